@@ -18,6 +18,13 @@ imports torch or touches a GPU -- starts N fresh child processes of this file (o
 `--backend gloo` is the CPU test switch: without a GPU it runs launch + shard + statistics exchange
 only (`"dry_run": true`, no kernel, no throughput claim) -- tests/test_bench_launch_cpu.py.
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, warm-up (clock ramp included), the K timed steps and
+the result line.  `--full` adds everything else the line has carried: the cold figure, the per-launch
+distribution, the torque checksums, the oracle parity samples and -- unless `--no-cpu-baseline` -- the
+informational objects (n32768, closed_loop, config1_gpu, cpu_baseline, vdot parity).
+`--dump-outputs DIR` writes what the last timed step returned (torques, metrics, status: float64 .npy files;
+the end-of-rollout statistics as rollout_stats.npy) after the timed region.
 """
 import argparse
 import hashlib
@@ -74,7 +81,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--per-gpu", type=int, default=4096, help="instances per GPU")
     ap.add_argument("--config", type=int, default=0, help="override workload config (2,3,4,5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: cold figure, per-launch distribution, checksums, oracle parity and the informational objects")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no oracle parity, CPU baseline or informational objects")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--variant", default="auto", choices=["auto", "hex"], help="kernel variant (one product family)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU work (seconds) for the baseline sample")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -402,6 +413,32 @@ def large_batch(device, steps=40):
             "status_nonzero": bad}
 
 
+DUMP_BYTES = 60 << 20                              # --dump-outputs: all ranks' files together stay under 64 MB
+STATS_FIELDS = ("ticks", "status_nonzero", "iters_sum", "tau_abs_sum", "tau_abs_max", "err_sum")
+
+
+def dump_outputs(path, out, st, rank, world):
+    """--dump-outputs: the last timed step's outputs as a caller of the path receives them -- tau [12][n], metrics [4][n], status [n] -- and
+    the end-of-rollout statistics (rank 0; gathered over the ranks) as float64 .npy files.  Ranks of an N > 1 run add `_rank<r>` to the name.
+    A shard too large for the byte budget keeps a fixed seeded sample of its instances, listed in instance_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tau, met, status = (t.cpu().numpy() for t in out)
+    arrays = {"tau": tau.astype(np.float64), "metrics": met.astype(np.float64), "status": status.astype(np.float64)}
+    n = status.shape[0]
+    per_instance = 8 * (tau.shape[0] + met.shape[0] + 2)       # + 1 for the instance index of a sample
+    budget = DUMP_BYTES // world
+    if n * per_instance > budget:
+        idx = np.sort(np.random.default_rng(20240).choice(n, budget // per_instance, replace=False))
+        arrays = {k: np.ascontiguousarray(v[..., idx]) for k, v in arrays.items()}
+        arrays["instance_index"] = idx.astype(np.float64)
+    if rank == 0:
+        arrays["rollout_stats"] = np.array([float(st[k]) for k in STATS_FIELDS] + [float(c) for c in st["mask_count"]], dtype=np.float64)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), arr)
+
+
 # ------------------------------------------------------------------------------------------------ one rank
 def run_rank(a):
     import numpy as np
@@ -421,6 +458,8 @@ def run_rank(a):
     dry = a.dry_run or (a.backend == "gloo" and not have_gpu)
     if not dry and not have_gpu:
         raise SystemExit("bench.py: no GPU visible -- the hot path has no CPU fallback (use --backend gloo for the dry-run test switch)")
+    if dry and a.dump_outputs:
+        raise SystemExit("bench.py: --dump-outputs needs the kernel path; a dry run computes nothing")
     use_pg = world > 1 or a.force_pg
     if use_pg:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -488,18 +527,20 @@ def run_rank(a):
     out = (torch.empty((12, n), dtype=torch.float64, device=dev), torch.empty((4, n), dtype=torch.float64, device=dev),
            torch.empty((n,), dtype=torch.int32, device=dev))
 
-    # cold figure first: W warm-up steps, then K timed steps BEFORE any clock ramp (what a process that ticks only now and
-    # then would see); reported as value_cold beside value
     bound = ctrl.bind(q, v, tg, mask, mu, ms, out=out)          # tensors validated once: the loops below are the C ABI only
-    for _ in range(a.warmup):
-        bound.step()
-    sync(); barrier(); sync()
-    t0c = time.perf_counter()
-    bound.time_steps(a.steps, wait=False)
-    ctrl.stats()
-    ms_cold = bound.time_steps_result()
-    sync(); barrier(); sync()
-    dt_cold = time.perf_counter() - t0c
+    # --full: the cold figure first: W warm-up steps, then K timed steps BEFORE any clock ramp (what a process that ticks only now and
+    # then would see); reported as value_cold beside value
+    dt_cold, ms_cold = 0.0, 0.0
+    if a.full:
+        for _ in range(a.warmup):
+            bound.step()
+        sync(); barrier(); sync()
+        t0c = time.perf_counter()
+        bound.time_steps(a.steps, wait=False)
+        ctrl.stats()
+        ms_cold = bound.time_steps_result()
+        sync(); barrier(); sync()
+        dt_cold = time.perf_counter() - t0c
 
     def rollout(steps):
         """K launches + the two events queued, the end-of-rollout statistics (reduction kernel, the ONE host wait, the gather: RCCL when world > 1),
@@ -545,10 +586,13 @@ def run_rank(a):
     # where this rank's region went (host clock, microseconds): queueing the K launches | the statistics reduction and the ONE wait | the gather | the closing bracket
     region_us = [round((ts[i + 1] - ts[i]) * 1e6, 1) for i in range(4)]
     per_rank_kernel_ms = [ms_per_launch]
-    # parity on EVERY rank: 64 instances spread over this rank's shard against the oracle (the checker), status of the whole shard
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, st, rank, world)
+    check = a.full and not a.no_cpu_baseline
+    # --full: parity on EVERY rank: 64 instances spread over this rank's shard against the oracle (the checker); status of the whole shard always
     par_rel, par_bad = 0.0, float((out[2] != 0).sum())        # par_bad: the DEVICE's count over the whole shard, nothing else
     par_obad, par_mis = 0.0, 0.0                                # oracle's non-zero statuses on the sample / sample instances whose status differs
-    if not a.no_cpu_baseline:
+    if check:
         from oracle import oracle_py as orc
         idx = np.unique(np.linspace(0, n - 1, min(64, n)).astype(int))
         sl = lambda x: None if x is None else (x[:, idx] if x.ndim == 2 else x[idx])
@@ -559,10 +603,9 @@ def run_rank(a):
         st_g = out[2][torch.tensor(idx, device=dev)].cpu().numpy()
         par_obad = float((st_o != 0).sum())
         par_mis = float((st_g != st_o).sum())
-    # checksum of this rank's torques of the last launch: FNV-1a 64 over the [12][n] doubles -- what examples/wbc_host.cpp prints for
+    # --full: checksum of this rank's torques of the last launch: FNV-1a 64 over the [12][n] doubles -- what examples/wbc_host.cpp prints for
     # the same shard (two hosts, one library: the same bits)
-    tau_bytes = out[0].cpu().numpy().tobytes()
-    tau_hash = fnv1a64(tau_bytes)
+    tau_hash = fnv1a64(out[0].cpu().numpy().tobytes()) if a.full else 0
     per_rank_rel, bad_total, obad_total, mis_total = [par_rel], par_bad, par_obad, par_mis
     per_rank_hash = ["%016x" % tau_hash]
     if use_pg:
@@ -576,8 +619,8 @@ def run_rank(a):
         bad_total, obad_total, mis_total = (float(allr[:, c].sum()) for c in (5, 6, 7))
         per_rank_hash = ["%016x" % ((int(allr[r, 8]) << 32) | int(allr[r, 9])) for r in range(world)]
         dt, ms_per_launch, dt_cold, ms_cold = (float(x) for x in allr[:, :4].max(0))     # MAX over ranks
-    # per-launch distribution (outside the timed region): one HIP event between every two launches
-    each, _ = ctrl.time_steps_each(a.steps, q, v, tg, mask, mu, ms, out=out)
+    # --full: per-launch distribution (outside the timed region): one HIP event between every two launches
+    each = ctrl.time_steps_each(a.steps, q, v, tg, mask, mu, ms, out=out)[0] if a.full else None
 
     if rank == 0:
         status = out[2].cpu().numpy()
@@ -642,7 +685,6 @@ def run_rank(a):
             # the same K launches without the region's fixed cost (stream start-up, statistics reduction and gather, one wake-up: ~30 us,
             # which weigh 1.5 us per step at the driver's K = 20 and 0.15 at K = 200): instances / slowest rank's HIP-event launch time
             "value_kernel_only": n_total / (ms_per_launch * 1e-3),
-            "value_cold": n_total * a.steps / dt_cold, "kernel_ms_cold": ms_cold,
             "region_us": {"queue_K_launches": region_us[0], "statistics_reduce_and_the_one_wait": region_us[1], "gather": region_us[2],
                           "closing_bracket": region_us[3], "total": round(dt * 1e6, 1), "device_time_of_the_K_launches": round(ms_per_launch * 1e3 * a.steps, 1),
                           "note": "rank 0's host clock inside the timed region"},
@@ -651,7 +693,6 @@ def run_rank(a):
             "dtype": "f64", "data": "synthetic", "backend": a.backend, "ramp_seconds": a.ramp_seconds,
             "ranks_seen": seen, "per_rank_ticks": [r["ticks"] for r in per_rank], "per_rank_kernel_ms": per_rank_kernel_ms,
             "process_group": (a.backend if use_pg else None), "kernel_src_sha16": kernel_src_sha16(),
-            "per_rank_tau_fnv1a64": per_rank_hash,
             "config": {"workload": "BASELINE configs[%d]: %d x %s, %s controller, %s" % (
                 cfg - 1, n_total, shard["model"], shard["kind"].upper(),
                 "trot contact masks" if cfg != 2 else "4-contact stand"),
@@ -665,9 +706,6 @@ def run_rank(a):
                          "kernel": "wbc_hex_kernel<%d, false>" % {"id": 0, "mptc": 1, "pc": 2, "clf": 3}[shard["kind"]],   # the name rocprofv3 prints
                          "kernel_law": shard["kind"].upper(),
                          "kernel_ms": ms_per_launch, "flops_per_tick": flops, "issued": issued,
-                         "kernel_ms_dist": {"median": float(np.median(each)), "p10": float(np.percentile(each, 10)),
-                                            "p90": float(np.percentile(each, 90)), "launches": int(each.size),
-                                            "how": "one HIP event between every two launches, after the timed region"},
                          "hbm": {"achieved_GBs": bpt * n / sec / 1e9, "peak_GBs": PEAK_HBM_GBS,
                                  "frac": bpt * n / sec / 1e9 / PEAK_HBM_GBS, "bytes_per_tick": bpt},
                          "bound_detail": "FP64 vector ALU: counted flops per tick x ticks / HIP-event launch time, priced against "
@@ -675,20 +713,27 @@ def run_rank(a):
                                          "kernel issues v_fma_f64, not MFMA (profiles/r02/micro_mfma_f64.md)",
                          "note": "HBM does not bind this path (SURVEY 8d): 864 algorithmic bytes per 37.6 kflop tick; HBM fraction stated beside it"},
             "status_nonzero": int(bad_total),                     # instances with status != 0 on the device: every rank's whole shard, summed
-            "oracle_status_nonzero": (int(obad_total) if not a.no_cpu_baseline else None),    # the oracle's, on the parity samples
-            "status_mismatch": (int(mis_total) if not a.no_cpu_baseline else None),           # sample instances where device and oracle disagree
-            "torque_rel_err_vs_cpu_ref": (max(per_rank_rel) if not a.no_cpu_baseline else None),
-            "per_rank_torque_rel_err": (per_rank_rel if not a.no_cpu_baseline else None),
+            "oracle_status_nonzero": (int(obad_total) if check else None),    # the oracle's, on the parity samples
+            "status_mismatch": (int(mis_total) if check else None),           # sample instances where device and oracle disagree
+            "torque_rel_err_vs_cpu_ref": (max(per_rank_rel) if check else None),
+            "per_rank_torque_rel_err": (per_rank_rel if check else None),
             "parity_sample": "64 instances spread over EVERY rank's shard against the oracle on that rank's host; maximum over ranks",
             "rollout_stats": {k: st[k] for k in ("ticks", "status_nonzero", "iters_sum", "tau_abs_max")},
             "iters_per_tick": st["iters_sum"] / max(1.0, st["ticks"]),
             "kernel_info": ctrl.kernel_info(),
         }
-        if world > 1 and not a.no_cpu_baseline:
+        if a.full:
+            line["value_cold"] = n_total * a.steps / dt_cold
+            line["kernel_ms_cold"] = ms_cold
+            line["per_rank_tau_fnv1a64"] = per_rank_hash
+            line["roofline"]["kernel_ms_dist"] = {"median": float(np.median(each)), "p10": float(np.percentile(each, 10)),
+                                                  "p90": float(np.percentile(each, 90)), "launches": int(each.size),
+                                                  "how": "one HIP event between every two launches, after the timed region"}
+        if world > 1 and check:
             # the N > 1 line carries the CPU baseline as well: rank 0's host cores on rank 0's shard (the other ranks wait at the
             # closing barrier; outside the timed region)
             line["cpu_baseline"] = cpu_baseline(shard, a.cpu_seconds)
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and check:
             line["n32768"] = large_batch(local)                       # informational, outside the timed region
             line["closed_loop"] = closed_loop(shard, local)           # informational, outside the timed region
             line["config1_gpu"] = config1_gpu(local)                  # BASELINE configs[0] on the product path (informational)

@@ -57,7 +57,7 @@ import pytest
 def test_self_launch_two_ranks_compute_on_the_gpu():
     """The self-launched N > 1 path with the REAL kernel: two rank processes, contiguous shards of BASELINE config 5's batch,
     one statistics all-gather -- both ranks share GPU 0 here (gloo test switch; RCCL needs one device per rank)."""
-    r = _run(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "5", "--warmup", "2", "--ramp-seconds", "0", "--per-gpu", "512",
+    r = _run(["--gpus", "2", "--full", "--backend", "gloo", "--share-gpu", "--steps", "5", "--warmup", "2", "--ramp-seconds", "0", "--per-gpu", "512",
               "--cpu-seconds", "0.5"], timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -103,7 +103,7 @@ print("rccl ok")
 def test_bench_one_gpu_through_the_process_group_branch():
     """bench.py --gpus 1 --force-pg: the N > 1 code path (RCCL init with device_id=, the device-side statistics gather, the
     per-rank timing gather) on the one GPU of this box; the line carries ranks_seen / per_rank_* for N = 1."""
-    r = _run(["--gpus", "1", "--force-pg", "--steps", "10", "--warmup", "2", "--ramp-seconds", "0.2", "--no-cpu-baseline"], timeout=900)
+    r = _run(["--gpus", "1", "--full", "--force-pg", "--steps", "10", "--warmup", "2", "--ramp-seconds", "0.2", "--no-cpu-baseline"], timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["process_group"] == "nccl" and d["n_gpus"] == 1 and d["ranks_seen"] == 1
@@ -153,7 +153,7 @@ def test_the_drivers_torchrun_line_two_real_ranks_sharing_the_gpu():
     8-GPU hand-over kit -- the line must match profiles/scale8_expected.json like a self-launched run does."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import scale8_expected as s8
-    r = _torchrun(2, ["--gpus", "2", "--config", "5", "--per-gpu", "4096", "--backend", "gloo", "--share-gpu", "--steps", "10", "--warmup", "2",
+    r = _torchrun(2, ["--gpus", "2", "--full", "--config", "5", "--per-gpu", "4096", "--backend", "gloo", "--share-gpu", "--steps", "10", "--warmup", "2",
                       "--ramp-seconds", "0", "--no-cpu-baseline"], timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     import tempfile
@@ -162,3 +162,50 @@ def test_the_drivers_torchrun_line_two_real_ranks_sharing_the_gpu():
     ok, rows = s8.check([f.name])
     os.unlink(f.name)
     assert ok, rows
+
+
+def test_dump_outputs_writes_float64_within_the_byte_budget(tmp_path, monkeypatch):
+    """--dump-outputs: tau / metrics / status of the last step and the statistics as float64 .npy; a shard over the budget keeps a fixed seeded sample."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    st = dict(ticks=40960.0, status_nonzero=0.0, iters_sum=9.0e4, tau_abs_sum=3.5e5, tau_abs_max=41.5, err_sum=2.0, mask_count=[float(k) for k in range(16)])
+    n = 4096
+    out = (torch.randn(12, n, dtype=torch.float64), torch.randn(4, n, dtype=torch.float64), torch.arange(n, dtype=torch.int32) % 3)
+    bench.dump_outputs(str(tmp_path / "all"), out, st, 0, 1)
+    got = {f[:-4]: np.load(str(tmp_path / "all" / f)) for f in os.listdir(str(tmp_path / "all"))}
+    assert sorted(got) == ["metrics", "rollout_stats", "status", "tau"] and all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["tau"], out[0].numpy()) and np.array_equal(got["status"], out[2].numpy())
+    assert got["rollout_stats"][0] == st["ticks"] and list(got["rollout_stats"][6:]) == st["mask_count"]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 64 * 1024)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), out, st, 1, 2)
+    files = sorted(os.listdir(str(tmp_path / "s1")))
+    assert files == ["instance_index_rank1.npy", "metrics_rank1.npy", "status_rank1.npy", "tau_rank1.npy"]      # rank 1: no statistics file
+    assert sum(os.path.getsize(str(tmp_path / "s1" / f)) for f in files) <= 64 * 1024 + 4 * 128                 # the budget + .npy headers
+    idx = np.load(str(tmp_path / "s1" / "instance_index_rank1.npy")).astype(int)
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "tau_rank1.npy")), out[0].numpy()[:, idx])
+    assert all(np.array_equal(np.load(str(tmp_path / "s1" / f)), np.load(str(tmp_path / "s2" / f))) for f in files)   # the same sample every run
+
+
+def test_dump_outputs_refused_on_a_dry_run(tmp_path):
+    r = _run(["--gpus", "1", "--backend", "gloo", "--dry-run", "--steps", "1", "--per-gpu", "64", "--dump-outputs", str(tmp_path / "d")], timeout=120)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not os.path.exists(str(tmp_path / "d"))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run: the K timed steps and the line, nothing of --full; --dump-outputs holds what the timed path returned."""
+    import numpy as np
+    r = _run(["--gpus", "1", "--steps", "10", "--warmup", "2", "--ramp-seconds", "0.2", "--dump-outputs", str(tmp_path)], timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 10 and d["rollout_stats"]["ticks"] == 4096 * 10 and abs(d["ms_per_step"] * 1e3 * 10 - d["region_us"]["total"]) < 1.0
+    for k in ("value_cold", "per_rank_tau_fnv1a64", "cpu_baseline", "closed_loop", "config1_gpu", "n32768"):
+        assert k not in d, k
+    assert "kernel_ms_dist" not in d["roofline"] and d["torque_rel_err_vs_cpu_ref"] is None
+    tau, met, status, stats = (np.load(str(tmp_path / (f + ".npy"))) for f in ("tau", "metrics", "status", "rollout_stats"))
+    assert tau.shape == (12, 4096) and met.shape == (4, 4096) and status.shape == (4096,) and tau.dtype == np.float64
+    assert np.isfinite(tau).all() and int((status != 0).sum()) == d["status_nonzero"]
+    assert stats[0] == d["rollout_stats"]["ticks"] and stats[2] == d["rollout_stats"]["iters_sum"] and stats[4] == d["rollout_stats"]["tau_abs_max"]

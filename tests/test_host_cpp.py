@@ -102,7 +102,7 @@ def test_cpp_host_equals_the_python_bench_on_the_same_batch(tmp_path):
         return _last_json(r.stdout)
 
     def bench():
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "5", "--per-gpu", "4096", "--steps", str(steps),
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--config", "5", "--per-gpu", "4096", "--steps", str(steps),
                             "--warmup", "20", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         return _last_json(r.stdout)

@@ -89,7 +89,7 @@ def test_one_gpu_runs_of_both_hosts_pass_the_checker(tmp_path):
     from quadruped_drake_amd import workloads
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     b = tmp_path / "bench_1.json"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "5", "--per-gpu", "4096", "--steps", "50", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--config", "5", "--per-gpu", "4096", "--steps", "50", "--warmup", "5",
                         "--no-cpu-baseline", "--ramp-seconds", "0.2"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     b.write_text(r.stdout)
@@ -114,7 +114,7 @@ def test_real_multi_rank_runs_sharing_one_gpu_match_the_predictions(world, tmp_p
     two ranks on one device, so the collective is gloo's; sharding, windows, launcher, statistics and the MAX over ranks are the N-GPU run's own).  Every
     rank's torque checksum and the gathered statistics must be the ones profiles/scale8_expected.json predicts for that N."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--config", "5", "--per-gpu", "4096", "--backend", "gloo", "--share-gpu",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full", "--config", "5", "--per-gpu", "4096", "--backend", "gloo", "--share-gpu",
                         "--steps", "10", "--warmup", "2", "--ramp-seconds", "0", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     f = tmp_path / ("bench_%d.json" % world); f.write_text(r.stdout)

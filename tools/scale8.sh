@@ -23,13 +23,13 @@ echo "GPUs visible: $ngpu"
 files=()
 for n in 1 2 4 8; do
   if [ "$share" = "--share-one-gpu" ] && [ "$n" -gt "$ngpu" ]; then
-    python3 bench.py --gpus $n --config 5 --per-gpu 4096 --backend gloo --share-gpu --steps 50 --warmup 5 --no-cpu-baseline > "$out/bench_shared_$n.json" 2> "$out/bench_shared_$n.err" \
+    python3 bench.py --gpus $n --full --config 5 --per-gpu 4096 --backend gloo --share-gpu --steps 50 --warmup 5 --no-cpu-baseline > "$out/bench_shared_$n.json" 2> "$out/bench_shared_$n.err" \
       && files+=("$out/bench_shared_$n.json") || echo "bench.py --gpus $n --share-gpu FAILED: $out/bench_shared_$n.err"
     continue
   fi
   [ "$n" -le "$ngpu" ] || { echo "N=$n skipped: only $ngpu GPU(s)"; continue; }
   # bench.py launches its own ranks for N > 1 (python -m torch.distributed.run --nproc-per-node N ... on 127.0.0.1)
-  python3 bench.py --gpus $n --config 5 --per-gpu 4096 --steps 200 --warmup 20 --no-cpu-baseline > "$out/bench_$n.json" 2> "$out/bench_$n.err" \
+  python3 bench.py --gpus $n --full --config 5 --per-gpu 4096 --steps 200 --warmup 20 --no-cpu-baseline > "$out/bench_$n.json" 2> "$out/bench_$n.err" \
     && files+=("$out/bench_$n.json") || echo "bench.py --gpus $n FAILED: $out/bench_$n.err"
   python3 -c "
 from quadruped_drake_amd import workloads
