@@ -13,12 +13,15 @@ c_i32_p = C.POINTER(C.c_int32)
 KIND_ID, KIND_MPTC, KIND_PC, KIND_CLF = 0, 1, 2, 3
 DEVICE_PTRS, HOST_PTRS = 0, 1
 
-# every symbol include/wbc.h (the controller interface) and include/wbc_extras.h (frozen out-of-scope exports) declare
+# every symbol include/wbc.h (the controller interface), include/wbc_plant.h (the plant step; prototypes in plant.py) and
+# include/wbc_extras.h (frozen out-of-scope exports) declare
 SYMBOLS = ["wbc_last_error", "wbc_version", "wbc_params_default", "wbc_create", "wbc_destroy", "wbc_set_stream",
            "wbc_step", "wbc_sync", "wbc_time_steps", "wbc_time_steps_result", "wbc_time_steps_each", "wbc_stats_get", "wbc_stats_reset", "wbc_stats_pack", "wbc_stats_reduce", "wbc_set_variant", "wbc_set_warm_start", "wbc_set_vdot_output", "wbc_integrate", "wbc_rollout",
            "wbc_kernel_info", "wbc_rollout_kernel_info", "wbc_variant_for", "wbc_trunk_state_decode", "wbc_trunk_state_to_targets", "wbc_traj_create",
            "wbc_traj_destroy", "wbc_traj_lookup", "wbc_robot_state_decode", "wbc_robot_state_encode",
-           "wbc_robot_states_unpack", "wbc_robot_controls_pack", "wbc_pd_step"]
+           "wbc_robot_states_unpack", "wbc_robot_controls_pack", "wbc_pd_step",
+           "wbc_plant_params_default", "wbc_plant_create", "wbc_plant_destroy", "wbc_plant_forward", "wbc_plant_step", "wbc_plant_rollout",
+           "wbc_plant_kernel_info"]
 
 
 class WbcModel(C.Structure):

@@ -1,0 +1,170 @@
+"""Batched rigid-contact plant step (include/wbc_plant.h): the robot that a closed loop's torques act on.
+
+`wbc_integrate` / `BatchedController.rollout` replay the controller's own plan (the QP's accelerations).  `RigidContactPlant`
+instead applies the controller's torques to a robot of its own -- the same kinematic tree with its own trunk mass scale, friction
+and actuator limit -- holds the stance feet with rigid contacts and reports, per instance and step, where a real ground would have
+let go (PULL, CONE), where a torque was clipped (CLIP) and what it could not answer (BAD).  `closed_loop` chains
+lookup -> controller tick -> plant step on the device.  Torch tensors and torch's current stream, as in controller.py.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+from .controller import load_model
+
+PULL, CONE, CLIP, BAD = 1, 2, 4, 8
+
+
+class WbcPlantParams(C.Structure):
+    _fields_ = [("Kd_contact", C.c_double), ("tau_max", C.c_double), ("mu", C.c_double)]
+
+
+_bound = None
+
+
+def _L():
+    """libwbc_hip.so with the prototypes of include/wbc_plant.h"""
+    global _bound
+    if _bound is None:
+        l = _lib.lib()
+        P = C.c_void_p
+        l.wbc_plant_params_default.argtypes = [C.POINTER(WbcPlantParams)]
+        l.wbc_plant_create.argtypes = [C.POINTER(_lib.WbcModel), C.POINTER(WbcPlantParams), C.c_int, C.POINTER(C.c_void_p)]
+        l.wbc_plant_destroy.argtypes = [P]
+        l.wbc_plant_forward.argtypes = [P, P, C.c_int, C.c_int] + [P] * 9
+        l.wbc_plant_step.argtypes = [P, P, C.c_int, C.c_int, C.c_double] + [P] * 11
+        l.wbc_plant_rollout.argtypes = [P, P, P, P, C.c_int, C.c_double, C.c_int, C.c_int] + [P] * 15
+        l.wbc_plant_kernel_info.argtypes = [P] + [C.POINTER(C.c_int)] * 4
+        _bound = l
+    return _bound
+
+
+def _dev_ptr(a, rows, n, tdt, name, device, optional=False):
+    import torch
+    if a is None:
+        if optional:
+            return None
+        raise ValueError(name + " is required")
+    if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == tdt and a.is_contiguous()):
+        raise ValueError("%s: expected a contiguous CUDA tensor of dtype %s" % (name, tdt))
+    if a.device.index != device:
+        raise ValueError("%s: tensor lives on cuda:%s, the plant on cuda:%d" % (name, a.device.index, device))
+    if tuple(a.shape) != ((rows, n) if rows else (n,)):
+        raise ValueError("%s: expected shape %s, got %s" % (name, (rows, n) if rows else (n,), tuple(a.shape)))
+    return C.c_void_p(a.data_ptr())
+
+
+class RigidContactPlant:
+    """Forward dynamics of N robots under applied torques, stance feet held by rigid contacts, semi-implicit Euler step.
+
+    model: name or path (as the controllers take it), or a model table; q_perm / act_perm as in the controllers.
+    kd_contact: the stance rows' velocity gain (the controllers' Kd_contact); tau_max: actuator limit (torques are clipped,
+    CLIP reported); mu: the plant's friction where no per-instance value is given (1.0: the reference's ground)."""
+
+    def __init__(self, model="mini_cheetah", device=0, kd_contact=100.0, tau_max=math.inf, mu=1.0, q_perm=None, act_perm=None):
+        self.table = load_model(model) if isinstance(model, str) else model
+        self.device = int(device)
+        L = _L()
+        m = _lib.WbcModel()
+        flat = np.asarray(self.table["flat"], dtype=np.float64)
+        assert flat.size == 215
+        m.flat[:] = flat.tolist()
+        m.q_perm[:] = list(range(12)) if q_perm is None else [int(x) for x in q_perm]
+        m.act_perm[:] = [int(x) for x in (self.table.get("act_perm", range(12)) if act_perm is None else act_perm)]
+        p = WbcPlantParams(float(kd_contact), float(tau_max), float(mu))
+        self.params = p
+        h = C.c_void_p()
+        _lib.check(L.wbc_plant_create(C.byref(m), C.byref(p), self.device, C.byref(h)))
+        self._h = h
+        self._L = L
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.wbc_plant_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _outs(self, n, out):
+        import torch
+        if out is not None:
+            return out
+        dev = "cuda:%d" % self.device
+        return (torch.empty((18, n), dtype=torch.float64, device=dev), torch.empty((12, n), dtype=torch.float64, device=dev),
+                torch.empty((n,), dtype=torch.int32, device=dev))
+
+    def _inputs(self, q, v, tau, contact_mask, mu, mass_scale):
+        import torch
+        n = int(q.shape[1])
+        d = self.device
+        return n, [_dev_ptr(q, 19, n, torch.float64, "q", d), _dev_ptr(v, 18, n, torch.float64, "v", d),
+                   _dev_ptr(tau, 12, n, torch.float64, "tau", d), _dev_ptr(contact_mask, 0, n, torch.uint8, "contact_mask", d),
+                   _dev_ptr(mu, 0, n, torch.float64, "mu", d, True), _dev_ptr(mass_scale, 0, n, torch.float64, "mass_scale", d, True)]
+
+    def forward(self, q, v, tau, contact_mask, mu=None, mass_scale=None, out=None):
+        """-> (vdot[18, N], force[12, N], flags[N]); q and v are not changed.  Asynchronous on torch's current stream."""
+        import torch
+        n, ins = self._inputs(q, v, tau, contact_mask, mu, mass_scale)
+        vd, f, fl = self._outs(n, out)
+        outs = [_dev_ptr(vd, 18, n, torch.float64, "vdot", self.device), _dev_ptr(f, 12, n, torch.float64, "force", self.device),
+                _dev_ptr(fl, 0, n, torch.int32, "flags", self.device)]
+        _lib.check(self._L.wbc_plant_forward(self._h, self._stream(), n, n, *ins, *outs))
+        return vd, f, fl
+
+    def step(self, q, v, tau, contact_mask, dt, time=None, mu=None, mass_scale=None, counts=None, out=None):
+        """forward, then the semi-implicit Euler step in place on q, v (time += dt when given; counts[4, N] int32: row b += 1
+        when flag bit b is raised).  -> (vdot, force, flags)"""
+        import torch
+        n, ins = self._inputs(q, v, tau, contact_mask, mu, mass_scale)
+        vd, f, fl = self._outs(n, out)
+        d = self.device
+        pt = _dev_ptr(time, 0, n, torch.float64, "time", d, True)
+        pc = _dev_ptr(counts, 4, n, torch.int32, "counts", d, True)
+        outs = [_dev_ptr(vd, 18, n, torch.float64, "vdot", d), _dev_ptr(f, 12, n, torch.float64, "force", d),
+                _dev_ptr(fl, 0, n, torch.int32, "flags", d)]
+        _lib.check(self._L.wbc_plant_step(self._h, self._stream(), n, n, float(dt), ins[0], ins[1], pt, *ins[2:], *outs, pc))
+        return vd, f, fl
+
+    def kernel_info(self):
+        """Registers, scratch bytes per lane, LDS bytes and threads per block of the plant-step kernel."""
+        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self._L.wbc_plant_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
+
+
+def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=None, plant_mu=None, plant_mass_scale=None, counts=None):
+    """`steps` x (target lookup at time -> ctrl tick -> plant step) on the device (wbc_plant_rollout), on torch's current stream.
+    Updates q, v, time in place; counts (int32 [4, N], optional) accumulates the plant's flag bits.  mu / mass_scale go to the
+    controller, plant_mu / plant_mass_scale to the plant.  Returns the last tick's (tau, metrics, status, targets, mask, force, flags)."""
+    import torch
+    if ctrl.host_ptrs:
+        raise ValueError("closed_loop: needs a device-pointer controller")
+    n = int(q.shape[1])
+    d = plant.device
+    ptr = lambda a, rows, dt_, name, opt=False: _dev_ptr(a, rows, n, dt_, name, d, opt)
+    pq, pv, pt = ptr(q, 19, torch.float64, "q"), ptr(v, 18, torch.float64, "v"), ptr(time, 0, torch.float64, "time")
+    pmu, pms = ptr(mu, 0, torch.float64, "mu", True), ptr(mass_scale, 0, torch.float64, "mass_scale", True)
+    ppmu, ppms = ptr(plant_mu, 0, torch.float64, "plant_mu", True), ptr(plant_mass_scale, 0, torch.float64, "plant_mass_scale", True)
+    pc = ptr(counts, 4, torch.int32, "counts", True)
+    dev = q.device
+    tg = torch.empty((54, n), dtype=torch.float64, device=dev); mk = torch.empty((n,), dtype=torch.uint8, device=dev)
+    tau = torch.empty((12, n), dtype=torch.float64, device=dev); met = torch.empty((4, n), dtype=torch.float64, device=dev)
+    st = torch.empty((n,), dtype=torch.int32, device=dev)
+    f = torch.zeros((12, n), dtype=torch.float64, device=dev); fl = torch.zeros((n,), dtype=torch.int32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    s = torch.cuda.current_stream(d).cuda_stream
+    _lib.check(plant._L.wbc_plant_rollout(ctrl._h, plant._h, traj._h, C.c_void_p(s), int(steps), float(dt), n, n, pq, pv, pt, p(tg),
+                                          p(mk), pmu, pms, ppmu, ppms, p(tau), p(met), p(st), p(f), p(fl), pc))
+    ctrl._bound_stream = s   # wbc_plant_rollout bound the controller to this stream (wbc_set_stream)
+    ctrl._keep = (tg, mk, tau, met, st, f, fl, mu, mass_scale, plant_mu, plant_mass_scale)
+    return tau, met, st, tg, mk, f, fl

@@ -1,0 +1,50 @@
+"""ctypes view of tools/libhost_plant.so: the plant math of csrc/wbc_plant.hpp instantiated on the host (tests only)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_LIB = None
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        so = os.path.join(_ROOT, "tools", "libhost_plant.so")
+        srcs = [os.path.join(_ROOT, "tools", "host_plant.cpp")] + [
+            os.path.join(_ROOT, "quadruped_drake_amd", "csrc", f) for f in ("wbc_plant.hpp", "wbc_tick.hpp", "wbc_model.hpp")]
+        if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(s) for s in srcs):
+            subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-ffp-contract=off", "-o", so, srcs[0]])
+        _LIB = C.CDLL(so)
+        _LIB.host_plant_batch.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 11)
+    return _LIB
+
+
+def _p(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def run(flat, q, v, tau, mask, mu=None, mass_scale=None, params3=None, q_perm=None, act_perm=None, dt=None, time=None, counts=None):
+    """Forward (dt None) or step.  Returns dict(vdot, force, flags[, q, v, time, counts]) -- copies, inputs untouched."""
+    q = np.array(q, dtype=np.float64, order="C"); v = np.array(v, dtype=np.float64, order="C")
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    n = q.shape[1]
+    flat = np.ascontiguousarray(flat, dtype=np.float64)
+    qp = np.ascontiguousarray(range(12) if q_perm is None else q_perm, dtype=np.int32)
+    ap = np.ascontiguousarray(range(12) if act_perm is None else act_perm, dtype=np.int32)
+    pr = None if params3 is None else np.ascontiguousarray(params3, dtype=np.float64)
+    mu = None if mu is None else np.ascontiguousarray(mu, dtype=np.float64)
+    ms = None if mass_scale is None else np.ascontiguousarray(mass_scale, dtype=np.float64)
+    tm = None if time is None else np.array(time, dtype=np.float64)
+    cn = None if counts is None else np.array(counts, dtype=np.int32)
+    vd = np.zeros((18, n)); f = np.zeros((12, n)); fl = np.zeros(n, np.int32)
+    rc = lib().host_plant_batch(_p(flat), _p(qp), _p(ap), _p(pr), n, n, 0 if dt is None else 1, 0.0 if dt is None else float(dt),
+                                _p(q), _p(v), _p(tm), _p(tau), _p(mask), _p(mu), _p(ms), _p(vd), _p(f), _p(fl), _p(cn))
+    assert rc == 0
+    out = dict(vdot=vd, force=f, flags=fl)
+    if dt is not None:
+        out.update(q=q, v=v, time=tm, counts=cn)
+    return out
