@@ -74,3 +74,52 @@ def step_batch(kind, m, p, q, v, targets, mask, mu=None, mass_scale=None, nthrea
                          mask.ctypes.data_as(C.POINTER(C.c_ubyte)), None if mu_a is None else _p(mu_a),
                          None if ms_a is None else _p(ms_a), _p(tau), _p(met), st.ctypes.data_as(C.POINTER(C.c_int)), int(nthreads))
     return tau, met, st
+
+
+def _ld(*arrays):
+    return tuple(np.ascontiguousarray(a, dtype=LD) for a in arrays)
+
+
+def model_scaled(name_or_table, mass_scale):
+    m = model(name_or_table)
+    m.base_mass *= mass_scale
+    for k in range(6):
+        m.base_I[k] *= mass_scale
+    return m
+
+
+def calc_dynamics(m, q, v):
+    """oracle_py.calc_dynamics in extended precision -> M[18,18], Cv[18], tau_g[18] as longdouble."""
+    q, v = _ld(q, v)
+    M = np.zeros((18, 18), LD); Cv = np.zeros(18, LD); tg = np.zeros(18, LD)
+    lib().orc_calc_dynamics(C.byref(m), _p(q), _p(v), _p(M), _p(Cv), _p(tg))
+    return M, Cv, tg
+
+
+def inverse_dynamics(m, q, v, vd, with_gravity=True):
+    q, v, vd = _ld(q, v, vd)
+    tau = np.zeros(18, LD)
+    lib().orc_inverse_dynamics(C.byref(m), _p(q), _p(v), _p(vd), int(with_gravity), _p(tau))
+    return tau
+
+
+def coriolis_matrix(m, q, v):
+    q, v = _ld(q, v)
+    Cm = np.zeros((18, 18), LD)
+    lib().orc_coriolis_matrix(C.byref(m), _p(q), _p(v), _p(Cm))
+    return Cm
+
+
+def foot_quantities(m, q, v, foot):
+    """oracle_py.foot_quantities in extended precision -> p[3], J[3,18], Jdot v[3]."""
+    q, v = _ld(q, v)
+    p = np.zeros(3, LD); J = np.zeros((3, 18), LD); Jdv = np.zeros(3, LD)
+    lib().orc_foot_quantities(C.byref(m), _p(q), _p(v), int(foot), _p(p), _p(J), _p(Jdv))
+    return p, J, Jdv
+
+
+def foot_jacobian_dot(m, q, v, foot):
+    q, v = _ld(q, v)
+    Jd = np.zeros((3, 18), LD)
+    lib().orc_foot_jacobian_dot(C.byref(m), _p(q), _p(v), int(foot), _p(Jd))
+    return Jd

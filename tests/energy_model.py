@@ -8,10 +8,15 @@ then uses Kane / d'Alembert projection:
     tau_g  = sum_b  m_b g Jc_b' e_z                           (== dU/dq N, reference sign)
     Cv     = sum_b  Jw_b' (Ic_b al_b + w_b x Ic_b w_b) + m_b Jc_b' a_b   with vdot = 0,
 
-where the body accelerations (al_b, a_b) at vdot = 0 are obtained by *numerically*
-differentiating the body twists J_b(q(t)) v along the exact flow qdot = N(q) v (central
-difference).  This is valid for Drake's quasi-velocities v = [w_WB(world), v_WBo(world), qd]
+where the body accelerations (al_b, a_b) at vdot = 0 come in two ways:
+  * exactly (bias_term_exact, dynamics_exact, foot_terms_exact, coriolis_matrix_indep): closed-form time derivatives of the
+    Jacobian columns, accumulated over the ancestors exactly as the Jacobians themselves are (bodies(..., v));
+  * by *numerically* differentiating the body twists J_b(q(t)) v along the exact flow qdot = N(q) v (bias_term,
+    foot_jacobian_dot_fd; central difference) -- kept as the check of the closed forms against this file's own FK.
+Both are valid for Drake's quasi-velocities v = [w_WB(world), v_WBo(world), qd]
 (the textbook Lagrange formula Mdot v - 1/2 grad(v'Mv) is NOT, because w is non-holonomic).
+Every function takes a dtype: float64, np.longdouble (this file's own rounding level) or complex (complex-step derivatives
+with respect to q, used for dJ/dq by the stand-in plant of tests/fake_pydrake).
 """
 import json
 import os
@@ -27,73 +32,104 @@ def load(name):
 
 
 def quat_R(q):
-    w, x, y, z = q / np.linalg.norm(q)
+    # sqrt(q.q), not np.linalg.norm: the same line then serves float64, longdouble and complex (complex-step) arguments
+    w, x, y, z = q / np.sqrt(q @ q)
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
                      [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
 
 
-def rodrigues(a, th):
-    a = np.asarray(a, float)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+def rodrigues(a, th, dtype=float):
+    a = np.asarray(a, dtype)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]], dtype)
+    return np.eye(3, dtype=dtype) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
 
 
 def skew(r):
-    return np.array([[0, -r[2], r[1]], [r[2], 0, -r[0]], [-r[1], r[0], 0]])
+    return np.array([[0, -r[2], r[1]], [r[2], 0, -r[0]], [-r[1], r[0], 0]], dtype=np.asarray(r).dtype)
 
 
-def I6_to_mat(I):
-    return np.array([[I[0], I[3], I[4]], [I[3], I[1], I[5]], [I[4], I[5], I[2]]])
+def cross(a, b):
+    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]])
 
 
-def bodies(model, q):
-    """List of dicts (R, p origin, mass, com_world, Ic_world, Jw 3x18, Jc 3x18) + feet (p, J)."""
-    q = np.asarray(q, float)
+def I6_to_mat(I, dtype=float):
+    return np.array([[I[0], I[3], I[4]], [I[3], I[1], I[5]], [I[4], I[5], I[2]]], dtype)
+
+
+def bodies(model, q, v=None, s=1.0, dtype=float):
+    """List of dicts (R, p origin, mass, com_world, Ic_world, Jw 3x18, Jc 3x18) + feet (p, J).
+
+    s: the trunk scale, with the meaning include/wbc.h gives mass_scale ("trunk mass/inertia scale"): the model's base link has
+    its mass and the inertia the model file states for it (about the link origin, base frame) multiplied by s; its CoM offset, a
+    length, stays.  With v (18 generalized velocities) every body also gets w = Jw v and the exact time derivatives Jwd, Jcd of
+    its Jacobians along qdot = N(q) v, and every foot Jd, column by column in closed form:
+      base columns of Jw and Jo are constant in the world frame;
+      a joint column of Jw is the axis a_w carried by its link:            d/dt a_w = w_link x a_w;
+      origin, CoM and foot columns are J - [r]x Jw with r carried by a link: d/dt  = Jd - [w_link x r]x Jw - [r]x Jwd.
+    dtype: float64 (default), np.longdouble (rounding level of this file) or complex (complex-step derivatives)."""
+    q = np.asarray(q, dtype)
+    dot = v is not None
+    if dot:
+        v = np.asarray(v, dtype)
     Rb = quat_R(q[:4]); pb = q[4:7]
     out = []
     feet = []
+    Z = np.zeros((3, 18), dtype)
 
-    def add(R, p, mass, com, I6, Jw, Jo):
-        c = R @ np.asarray(com)
-        Io = R @ I6_to_mat(I6) @ R.T
-        Ic = Io - mass * (c @ c * np.eye(3) - np.outer(c, c))
+    def add(R, p, mass, com, I6, Jw, Jo, Jwd, Jod):
+        c = R @ np.asarray(com, dtype)
+        Io = R @ I6_to_mat(I6, dtype) @ R.T
+        Ic = Io - mass * (c @ c * np.eye(3, dtype=dtype) - np.outer(c, c))
         Jc = Jo - skew(c) @ Jw  # v_c = v_o + w x c
-        out.append(dict(R=R, p=p, m=mass, c=p + c, Ic=Ic, Jw=Jw, Jc=Jc))
+        b = dict(R=R, p=p, m=mass, c=p + c, Ic=Ic, Jw=Jw, Jc=Jc)
+        if dot:
+            w = Jw @ v
+            b.update(w=w, Jwd=Jwd, Jcd=Jod - skew(cross(w, c)) @ Jw - skew(c) @ Jwd)
+        out.append(b)
 
-    Jw0 = np.zeros((3, 18)); Jw0[:, 0:3] = np.eye(3)
-    Jo0 = np.zeros((3, 18)); Jo0[:, 3:6] = np.eye(3)
+    Jw0 = np.zeros((3, 18), dtype); Jw0[:, 0:3] = np.eye(3)
+    Jo0 = np.zeros((3, 18), dtype); Jo0[:, 3:6] = np.eye(3)
     b = model["base"]
-    add(Rb, pb, b["mass"], b["com"], b["I"], Jw0, Jo0)
+    sb = np.asarray(s, dtype)
+    add(Rb, pb, sb * b["mass"], b["com"], sb * np.asarray(b["I"], dtype), Jw0, Jo0, Z, Z)
     for l, leg in enumerate(model["legs"]):
-        R, p, Jw, Jo = Rb, pb, Jw0, Jo0
+        R, p, Jw, Jo, Jwd, Jod = Rb, pb, Jw0, Jo0, Z, Z
         for k, L in enumerate(leg["links"]):
-            off = R @ np.asarray(L["off"])
-            a_w = R @ np.asarray(L["axis"])
+            off = R @ np.asarray(L["off"], dtype)
+            a_w = R @ np.asarray(L["axis"], dtype)
+            if dot:
+                w = Jw @ v      # of the parent link, which carries both off and the joint axis
+                Jod = Jod - skew(cross(w, off)) @ Jw - skew(off) @ Jwd
+                Jwd = Jwd.copy()
+                Jwd[:, 6 + 3 * l + k] = cross(w, a_w)
             # origin of the child moves with the parent: v_o' = v_o + w x off
             Jo = Jo - skew(off) @ Jw
             p = p + off
             Jw = Jw.copy()
             Jw[:, 6 + 3 * l + k] = a_w
-            R = R @ rodrigues(L["axis"], q[7 + 3 * l + k])
-            add(R, p, L["mass"], L["com"], L["I"], Jw, Jo)
-        d = R @ np.asarray(leg["foot_off"])
-        feet.append(dict(p=p + d, J=Jo - skew(d) @ Jw))
+            R = R @ rodrigues(L["axis"], q[7 + 3 * l + k], dtype)
+            add(R, p, L["mass"], L["com"], L["I"], Jw, Jo, Jwd, Jod)
+        d = R @ np.asarray(leg["foot_off"], dtype)
+        f = dict(p=p + d, J=Jo - skew(d) @ Jw)
+        if dot:
+            f["Jd"] = Jod - skew(cross(Jw @ v, d)) @ Jw - skew(d) @ Jwd
+        feet.append(f)
     return out, feet
 
 
-def mass_matrix(model, q):
-    bs, _ = bodies(model, q)
-    M = np.zeros((18, 18))
+def mass_matrix(model, q, s=1.0, dtype=float):
+    bs, _ = bodies(model, q, s=s, dtype=dtype)
+    M = np.zeros((18, 18), dtype)
     for b in bs:
         M += b["Jw"].T @ b["Ic"] @ b["Jw"] + b["m"] * b["Jc"].T @ b["Jc"]
     return M
 
 
-def gravity_term(model, q):
-    bs, _ = bodies(model, q)
+def gravity_term(model, q, s=1.0, dtype=float):
+    bs, _ = bodies(model, q, s=s, dtype=dtype)
     g = model["gravity"]
-    t = np.zeros(18)
+    t = np.zeros(18, dtype)
     for b in bs:
         t += b["m"] * g * b["Jc"][2, :]
     return t
@@ -137,7 +173,7 @@ def bias_term(model, q, v, h=1e-5):
         w = b0["Jw"] @ v
         al = (bp["Jw"] @ v - bm["Jw"] @ v) / (2 * h)
         ac = (bp["Jc"] @ v - bm["Jc"] @ v) / (2 * h)
-        out += b0["Jw"].T @ (b0["Ic"] @ al + np.cross(w, b0["Ic"] @ w)) + b0["m"] * b0["Jc"].T @ ac
+        out += b0["Jw"].T @ (b0["Ic"] @ al + cross(w, b0["Ic"] @ w)) + b0["m"] * b0["Jc"].T @ ac
     return out
 
 
@@ -145,6 +181,72 @@ def foot_jacobian_dot_fd(model, q, v, foot, h=1e-5):
     _, fp = bodies(model, flow(q, v, h))
     _, fm = bodies(model, flow(q, v, -h))
     return (fp[foot]["J"] - fm[foot]["J"]) / (2 * h)
+
+
+# ---- exact (closed-form) velocity-product terms: no finite difference anywhere.  The functions above stay as their check
+# (tests/test_oracle_dynamics.py::test_exact_terms_vs_own_differences).
+def bias_term_exact(model, q, v, s=1.0, dtype=float):
+    """C(q,v)v by Kane projection with the closed-form body accelerations at vdot = 0 (al = Jwd v, a_c = Jcd v)."""
+    bs, _ = bodies(model, q, v, s, dtype)
+    v = np.asarray(v, dtype)
+    out = np.zeros(18, dtype)
+    for b in bs:
+        w = b["w"]
+        out += b["Jw"].T @ (b["Ic"] @ (b["Jwd"] @ v) + cross(w, b["Ic"] @ w)) + b["m"] * b["Jc"].T @ (b["Jcd"] @ v)
+    return out
+
+
+def inverse_dynamics_exact(model, q, v, vd, s=1.0, dtype=float):
+    """M vd + Cv + tau_g from one pass over the bodies (al = Jw vd + Jwd v, ...)."""
+    bs, _ = bodies(model, q, v, s, dtype)
+    v = np.asarray(v, dtype); vd = np.asarray(vd, dtype)
+    e_z = np.array([0, 0, model["gravity"]], dtype)
+    out = np.zeros(18, dtype)
+    for b in bs:
+        w = b["w"]
+        al = b["Jw"] @ vd + b["Jwd"] @ v
+        ac = b["Jc"] @ vd + b["Jcd"] @ v
+        out += b["Jw"].T @ (b["Ic"] @ al + cross(w, b["Ic"] @ w)) + b["m"] * b["Jc"].T @ (ac + e_z)
+    return out
+
+
+def foot_terms_exact(model, q, v, dtype=float):
+    """[(p, J, Jdot, Jdot v)] for the four feet."""
+    _, feet = bodies(model, q, v, dtype=dtype)
+    v = np.asarray(v, dtype)
+    return [(f["p"], f["J"], f["Jd"], f["Jd"] @ v) for f in feet]
+
+
+def foot_jacobian_dot_exact(model, q, v, foot, dtype=float):
+    return foot_terms_exact(model, q, v, dtype)[foot][2]
+
+
+def foot_jdot_v_exact(model, q, v, foot, dtype=float):
+    return foot_terms_exact(model, q, v, dtype)[foot][3]
+
+
+def coriolis_matrix_indep(model, q, v, s=1.0, dtype=float):
+    """C = 1/2 dCv/dv (the definition the reference's autodiff recipe uses): central differences of the exact Cv with step 1,
+    exact for a quadratic form up to rounding."""
+    v = np.asarray(v, dtype)
+    C = np.zeros((18, 18), dtype)
+    for j in range(18):
+        e = np.zeros(18, dtype); e[j] = 1
+        C[:, j] = (bias_term_exact(model, q, v + e, s, dtype) - bias_term_exact(model, q, v - e, s, dtype)) / 4
+    return C
+
+
+def dynamics_exact(model, q, v, s=1.0, dtype=float):
+    """(M, Cv, tau_g) from one FK pass."""
+    bs, _ = bodies(model, q, v, s, dtype)
+    v = np.asarray(v, dtype)
+    M = np.zeros((18, 18), dtype); Cv = np.zeros(18, dtype); tg = np.zeros(18, dtype)
+    for b in bs:
+        w = b["w"]
+        M += b["Jw"].T @ b["Ic"] @ b["Jw"] + b["m"] * b["Jc"].T @ b["Jc"]
+        Cv += b["Jw"].T @ (b["Ic"] @ (b["Jwd"] @ v) + cross(w, b["Ic"] @ w)) + b["m"] * b["Jc"].T @ (b["Jcd"] @ v)
+        tg += b["m"] * model["gravity"] * b["Jc"][2, :]
+    return M, Cv, tg
 
 
 def rpy_from_R(R):

@@ -6,7 +6,8 @@ derivatives, NOT by handing over the oracle's own C / Jdot:
   * CalcBiasTerm on velocities seeded with derivatives (basic_controller.py:117-132): dCv/dv by central differences with
     step 1 -- exact for the quadratic form Cv;
   * CalcJacobianTranslationalVelocity on positions seeded with derivatives (basic_controller.py:198-220): dJ/dq by
-    Richardson-extrapolated central differences of the oracle's foot Jacobian (error ~1e-11).
+    Richardson-extrapolated central differences of the oracle's foot Jacobian (error ~1e-11); the "energy" backend serves
+    the same derivative by complex-step differentiation of its own FK.
 So a run of the reference's ControlLaw over this plant checks the oracle's Coriolis matrix and Jdot against the
 reference's DEFINITIONS of them, and everything downstream against the reference's own arithmetic."""
 import numpy as np
@@ -74,6 +75,7 @@ class RefPlant:
         self.pv = np.array(list(range(6)) + [6 + o for o in self.order])      # canonical i  <->  plant pv[i]
         self.pq = np.array(list(range(7)) + [7 + o for o in self.order])
         self.m = orc.model(model_name)
+        self.s = 1.0                            # trunk scale of the "energy" backend (set_trunk_scale)
         self.backend = backend
         if backend == "energy":
             import energy_model as em           # tests/energy_model.py: the independent numpy derivation
@@ -81,23 +83,28 @@ class RefPlant:
         else:
             assert backend == "oracle"
 
+    def set_trunk_scale(self, s):
+        """The trunk mass / inertia scale of include/wbc.h's mass_scale, for whichever backend serves the terms."""
+        self.m = orc.model_scaled(self.model_name, float(s))
+        self.s = float(s)
+
     # ---- rigid-body terms in canonical order: oracle/ (default) or tests/energy_model.py ("energy": plain FK + Kane
-    # projection, accelerations by Richardson-extrapolated differences along the exact flow; nothing shared with oracle/)
+    # projection with closed-form body accelerations, no finite difference; nothing shared with oracle/)
     def _dyn(self, q, v):
         if self.backend == "oracle":
             return orc.calc_dynamics(self.m, q, v)
-        em, t = self._em, self._emodel
-        rich = lambda f, h: (4.0 * f(0.5 * h) - f(h)) / 3.0
-        return em.mass_matrix(t, q), rich(lambda h: em.bias_term(t, q, v, h), 2e-3), em.gravity_term(t, q)
+        return self._em.dynamics_exact(self._emodel, q, v, self.s)
+
+    def _cv(self, q, v):
+        if self.backend == "oracle":
+            return orc.calc_dynamics(self.m, q, v)[1]
+        return self._em.bias_term_exact(self._emodel, q, v, self.s)
 
     def _foot(self, q, v, foot):
         if self.backend == "oracle":
             return orc.foot_quantities(self.m, q, v, foot)
-        em, t = self._em, self._emodel
-        f = em.bodies(t, q)[1][foot]
-        rich = lambda g, h: (4.0 * g(0.5 * h) - g(h)) / 3.0
-        Jd = rich(lambda h: em.foot_jacobian_dot_fd(t, q, v, foot, h), 2e-3)
-        return np.array(f["p"], dtype=float), np.array(f["J"], dtype=float), Jd @ v
+        p, J, _, Jdv = self._em.foot_terms_exact(self._emodel, q, v)[foot]
+        return np.array(p, dtype=float), np.array(J, dtype=float), np.array(Jdv, dtype=float)
 
     def _body(self, q, v):
         if self.backend == "oracle":
@@ -210,7 +217,7 @@ class RefPlant:
         dC = np.zeros((18, 18))
         for j in range(18):
             e = np.zeros(18); e[j] = 1.0
-            dC[:, j] = 0.5 * (self._dyn(ctx.q, ctx.v + e)[1] - self._dyn(ctx.q, ctx.v - e)[1])
+            dC[:, j] = 0.5 * (self._cv(ctx.q, ctx.v + e) - self._cv(ctx.q, ctx.v - e))
         return join(self._vec(Cv), self._vec(dC @ ctx.vD))
 
     def CalcGravityGeneralizedForces(self, ctx):
@@ -247,6 +254,14 @@ class RefPlant:
             return self._cols(J)
         assert self.autodiff
         dJ = np.zeros((3, 18, 19))
+        if self.backend == "energy":
+            # complex step on the independent FK: dJ/dq_k = Im J(q + i h e_k) / h, derivative-exact (no subtraction), the four
+            # quaternion coordinates included (quat_R normalises by sqrt(q.q), which is analytic)
+            h = 1e-30
+            for k in range(19):
+                qc = np.array(ctx.q, dtype=complex); qc[k] += 1j * h
+                dJ[:, :, k] = self._em.bodies(self._emodel, qc, dtype=complex)[1][foot]["J"].imag / h
+            return join(self._cols(J), self._cols(dJ @ ctx.qD))
         for k in range(19):
             e = np.zeros(19); e[k] = 1.0
             d = lambda h: (self._J(ctx.q + h * e, ctx.v, foot) - self._J(ctx.q - h * e, ctx.v, foot)) / (2.0 * h)

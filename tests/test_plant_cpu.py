@@ -1,5 +1,7 @@
 """Rigid-contact plant step (include/wbc_plant.h), no GPU: the host instantiation of csrc/wbc_plant.hpp against the dense numpy
-plant (tests/plant_oracle.py), and the argument checks of the C ABI that return before any device is touched."""
+plant (tests/plant_oracle.py), and the argument checks of the C ABI that return before any device is touched.  The dense plant
+runs over both of its backends at the same tolerances: "oracle" (terms of oracle/) and "energy" (closed-form terms of
+tests/energy_model.py, trunk scale included; nothing of oracle/ in the loop)."""
 import ctypes as C
 
 import numpy as np
@@ -10,6 +12,7 @@ import plant_oracle as po
 from quadruped_drake_amd import load_model, workloads
 
 MODELS = [(3, "mini_cheetah"), (4, "anymal_b")]
+BACKENDS = ["oracle", "energy"]
 
 
 def _draw(cfg, n, seed):
@@ -31,13 +34,16 @@ def test_host_plant_matches_dense_oracle(cfg, model):
     b, tau, mask, sp = _draw(cfg, n, 11)
     t = load_model(model)
     out = hp.run(t["flat"], b["q"], b["v"], tau, mask, mass_scale=sp, act_perm=t.get("act_perm"))
-    vd, f, fl = po.forward(t, b["q"], b["v"], tau, mask, mass_scale=sp)
-    assert _rel(out["vdot"], vd) < 1e-10
-    assert _rel(out["force"], f) < 1e-10
-    keep = np.array([po.margin(t, b["q"][:, i], b["v"][:, i], tau[:, i], int(mask[i]), 1.0, sp[i]) > 1e-6 for i in range(n)])
-    assert keep.sum() > 0.9 * n
-    assert (out["flags"][keep] == fl[keep]).all()
-    assert ((fl & (po.PULL | po.CONE)) != 0).any() and ((fl & (po.PULL | po.CONE)) == 0).any()   # both outcomes are exercised
+    for backend in BACKENDS:
+        vd, f, fl = po.forward(t, b["q"], b["v"], tau, mask, mass_scale=sp, backend=backend)
+        assert _rel(out["vdot"], vd) < 1e-10, backend
+        assert _rel(out["force"], f) < 1e-10, backend
+        # the draws left out of the flag comparison are chosen by this backend alone, and stay within the cap
+        keep = np.array([po.margin(t, b["q"][:, i], b["v"][:, i], tau[:, i], int(mask[i]), 1.0, sp[i], backend=backend) > 1e-6
+                         for i in range(n)])
+        assert keep.sum() > 0.9 * n, backend
+        assert (out["flags"][keep] == fl[keep]).all(), backend
+        assert ((fl & (po.PULL | po.CONE)) != 0).any() and ((fl & (po.PULL | po.CONE)) == 0).any()   # both outcomes are exercised
     assert (out["force"][np.repeat(((mask[None, :] >> np.arange(4)[:, None]) & 1) == 0, 3, axis=0)] == 0).all()   # swing feet: 0
 
 
@@ -48,8 +54,9 @@ def test_host_plant_step_matches_dense_oracle(cfg, model):
     t = load_model(model)
     time = np.linspace(0.0, 1.0, n); counts = np.zeros((4, n), np.int32)
     out = hp.run(t["flat"], b["q"], b["v"], tau, mask, mass_scale=sp, act_perm=t.get("act_perm"), dt=2e-3, time=time, counts=counts)
-    qn, vn, vd, f, fl = po.step(t, b["q"], b["v"], tau, mask, 2e-3, mass_scale=sp)
-    assert _rel(out["q"], qn) < 1e-12 and _rel(out["v"], vn) < 1e-10
+    for backend in BACKENDS:
+        qn, vn, vd, f, fl = po.step(t, b["q"], b["v"], tau, mask, 2e-3, mass_scale=sp, backend=backend)
+        assert _rel(out["q"], qn) < 1e-12 and _rel(out["v"], vn) < 1e-10, backend
     assert np.array_equal(out["time"], time + 2e-3)
     for bit in range(4):
         assert np.array_equal(out["counts"][bit], (out["flags"] >> bit) & 1)
@@ -67,8 +74,9 @@ def test_straight_stance_knee_is_answered():
     out = hp.run(t["flat"], q, v, tau, mask, act_perm=t.get("act_perm"))
     assert (out["flags"] & po.BAD == 0).all()
     assert np.isfinite(out["vdot"]).all() and np.isfinite(out["force"]).all()
-    vd, f, fl = po.forward(t, q, v, tau, mask)
-    assert _rel(out["vdot"], vd) < 1e-8 and _rel(out["force"], f) < 1e-8
+    for backend in BACKENDS:
+        vd, f, fl = po.forward(t, q, v, tau, mask, backend=backend)
+        assert _rel(out["vdot"], vd) < 1e-8 and _rel(out["force"], f) < 1e-8, backend
 
 
 def test_non_finite_input_is_bad_and_leaves_state():
@@ -90,14 +98,15 @@ def test_torque_clipping_against_oracle():
     b, tau, mask, sp = _draw(4, 128, 9)
     tm = 20.0
     out = hp.run(t["flat"], b["q"], b["v"], tau, mask, mass_scale=sp, act_perm=t.get("act_perm"), params3=[100.0, tm, 1.0])
-    vd, f, fl = po.forward(t, b["q"], b["v"], tau, mask, mass_scale=sp, tau_max=tm)
-    assert _rel(out["vdot"], vd) < 1e-10 and _rel(out["force"], f) < 1e-10
     clip = (np.abs(tau) > tm).any(0)
     assert clip.any() and not clip.all()
     assert np.array_equal((out["flags"] & po.CLIP) != 0, clip)
-    # clipping changes the answer: the unclipped dense plant differs
-    vd_u, _, _ = po.forward(t, b["q"], b["v"], tau, mask, mass_scale=sp)
-    assert _rel(vd_u[:, clip], vd[:, clip]) > 1e-3
+    for backend in BACKENDS:
+        vd, f, fl = po.forward(t, b["q"], b["v"], tau, mask, mass_scale=sp, tau_max=tm, backend=backend)
+        assert _rel(out["vdot"], vd) < 1e-10 and _rel(out["force"], f) < 1e-10, backend
+        # clipping changes the answer: the unclipped dense plant differs
+        vd_u, _, _ = po.forward(t, b["q"], b["v"], tau, mask, mass_scale=sp, backend=backend)
+        assert _rel(vd_u[:, clip], vd[:, clip]) > 1e-3
 
 
 # ---- C ABI argument checks that return before any device is touched

@@ -63,6 +63,13 @@ def test_device_plant_matches_dense_oracle(cfg):
     assert keep.sum() > 0.9 * idx.size
     assert np.array_equal(fl[idx][keep], flo[keep])
     assert ((flo & (po.PULL | po.CONE)) != 0).any()
+    # and with nothing of oracle/ in the loop: the closed-form terms of tests/energy_model.py, trunk scale included
+    vde, fe, fle = po.forward(t, b["q"], b["v"], tau, mask, mass_scale=sp, idx=idx, backend="energy")
+    assert _rel(vd[:, idx], vde) < 1e-9 and _rel(f[:, idx], fe) < 1e-9
+    keep_e = np.array([po.margin(t, b["q"][:, i], b["v"][:, i], tau[:, i], int(mask[i]), 1.0, sp[i], backend="energy") > 1e-6
+                       for i in idx])
+    assert keep_e.sum() > 0.9 * idx.size
+    assert np.array_equal(fl[idx][keep_e], fle[keep_e])
     plant.close()
 
 
@@ -131,7 +138,8 @@ def test_closed_loop_equals_plan_following_rollout(kind, dt):
 
 
 def test_mismatched_closed_loop_every_tick_against_oracle():
-    """Plant trunk 0.8 - 1.2 x the controller's: every tick's device plant step equals the dense numpy plant on the same q, v, tau."""
+    """Plant trunk 0.8 - 1.2 x the controller's: every tick's device plant step equals the dense numpy plant on the same q, v, tau;
+    on every 10th tick also the dense plant over the independent terms (backend "energy"), for 64 of the 256 instances."""
     import torch
     from quadruped_drake_amd import IDController, RigidContactPlant
     from quadruped_drake_amd.trajectory import TrunkTrajectory
@@ -160,6 +168,10 @@ def test_mismatched_closed_loop_every_tick_against_oracle():
         if diff.any():
             for i in np.flatnonzero(diff):
                 assert po.margin(t, qh[:, i], vh[:, i], tauh[:, i], int(mkh[i]), 1.0, sp[i]) < 1e-6, (k, i, fl[i], flo[i])
+        if k % 10 == 0:
+            qe, ve, vde, fe, fle = po.step(t, qh[:, :64], vh[:, :64], tauh[:, :64], mkh[:64], dt, mass_scale=sp[:64], backend="energy")
+            assert _rel(vd.cpu().numpy()[:, :64], vde) < 1e-9 and _rel(f.cpu().numpy()[:, :64], fe) < 1e-9, k
+            assert _rel(q.cpu().numpy()[:, :64], qe) < 1e-9 and _rel(v.cpu().numpy()[:, :64], ve) < 1e-9, k
         worst = max(worst, _rel(q.cpu().numpy(), qo))
     assert np.isfinite(q.cpu().numpy()).all()
     plant.close(); ctrl.close()

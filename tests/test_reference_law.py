@@ -5,7 +5,9 @@ stand-ins for the Drake plant and for MathematicalProgram / the solver).
 What this pins: the arithmetic the reference's Python defines -- targets and gains, RPY handling, Lambda / Jbar / Q /
 f_des, the Coriolis-matrix and Jdot definitions, QP assembly, logging -- for ID, MPTC, PC, CLF, every contact mask,
 both robots, randomised mu / mass.  What it does not: Drake's rigid-body numbers (the stand-in plant takes them from
-oracle/) and OSQP's pick among the optimal set (the stand-in solver applies this repository's tie-break).
+oracle/, or in the indep_* sets from the closed-form independent model of tests/energy_model.py, which
+tests/test_oracle_dynamics.py holds against oracle/ at 1e-13) and OSQP's pick among the optimal set (the stand-in solver
+applies this repository's tie-break).
 Tolerances: solver-independent quantities (vd, metrics) 1e-7; torques 1e-5 relative (north_star: 1e-4) -- the
 stand-in solves the Hessian form the reference assembles (J'J, G'WG), which carries less of the eps2 tie-break's
 precision than the square-root form the oracle and the kernels factor; measured worst case 9e-7."""
@@ -20,7 +22,10 @@ SETS = ["cfg2_id", "cfg3_id", "cfg3_mptc", "cfg4_anymal_mptc", "cfg5_rand_mptc",
         # simulate.py's initial state with the dictionaries of the reference's planner scenarios (planner + controller chained)
         "scen_id", "scen_mptc", "scen_pc", "scen_clf",
         # the same reference code over a plant backed by tests/energy_model.py instead of oracle/: nothing shared at all
-        "indep_cfg2_id", "indep_cfg3_mptc", "indep_cfg4_anymal_mptc", "indep_cfg3_clf", "indep_cfg3_pc"]
+        # (closed-form terms, trunk scale included; 64 instances each, 32 for the ANYmal and saturated-stand variants, every mask)
+        "indep_cfg2_id", "indep_cfg3_mptc", "indep_cfg4_anymal_mptc", "indep_cfg3_clf", "indep_cfg3_pc", "indep_cfg5_rand_mptc",
+        "indep_masks16_id", "indep_masks16_mptc", "indep_masks16_pc", "indep_masks16_clf",
+        "indep_cfg4_anymal_id", "indep_cfg4_anymal_clf", "indep_cfg4_anymal_pc", "indep_cfg2_mptc", "indep_cfg2_pc", "indep_cfg2_clf"]
 PERM_SETS = ["perm_cfg2_id", "perm_cfg3_mptc", "perm_cfg4_anymal_mptc"]   # plant with its own joint / actuator numbering
 TAU_TOL, IND_TOL = 1e-5, 1e-7
 
