@@ -1,0 +1,104 @@
+/*
+ * wbc_ground.h -- C ABI of the batched compliant-ground plant (libwbc_hip.so, next to include/wbc.h and include/wbc_plant.h).
+ *
+ * The rigid-contact plant of wbc_plant.h holds every scheduled stance foot with a bilateral constraint and only reports where a real
+ * ground would have let go.  This plant has a ground: the plane z = 0, a compliant half-space that touches each foot in a point.
+ * The ground force is an explicit function of the state, so a foot that is lifted is free, a foot that lands is caught, a foot whose
+ * tangential load exceeds the friction cone slides, and a robot that tips falls.  No contact schedule enters.
+ *
+ * The model (this project's definition; unpinned at Drake like every other number here).  For foot c with world position p_c and
+ * velocity pd_c = J_c v:
+ *   phi = foot_radius - p_c,z.   If phi <= 0:  f_c = 0, exactly.   Otherwise
+ *   f_n = stiffness * phi * max(0, 1 - dissipation * pd_c,z)                       (Hunt-Crossley)
+ *   v_t = (pd_x, pd_y),   f_t = -mu_p f_n v_t / max(|v_t|, v_stiction),   f_c = (f_t, f_n).
+ * Below v_stiction the friction force is a viscous damper, so a loaded foot under a tangential load CREEPS, at up to v_stiction.
+ * One substep of length h = dt / S, everything evaluated at the substep's start state:
+ *   tau_a = clip(tau, -tau_max, +tau_max), held over the whole step, mapped to S' tau_a through act_perm / q_perm;
+ *   M vd + Cv + tau_g = S' tau_a + w_ext + sum_c J_c' f_c,   the trunk mass and inertia scaled by s_p exactly as wbc_plant scales it;
+ *   w_ext: an optional external wrench on the trunk, ext_wrench [6][ld], world frame, rows as v's base rows ([torque about the trunk
+ *   origin; force]), held over the step (the push of a push-recovery test);
+ *   then the arithmetic of wbc_integrate with step h.
+ * S = ceil(dt / max_substep) is computed on the host (with 1e-12 relative slack, so that dt = 8 max_substep gives 8); all S substeps
+ * of a step run inside one kernel launch with the state in registers.
+ * Defaults (wbc_ground_params_default): stiffness = (the robot's weight at s_p = 1) / delta with delta = 1e-3 m, dissipation =
+ * 1 / sqrt(g delta) -- the estimate Drake documents for its penetration allowance --, mu = 1.0 (the reference's ground,
+ * simulate.py:43-46), v_stiction = 0.05 m/s, foot_radius = 0, tau_max = +inf, max_substep = 6.25e-5 s (16 substeps of a 1 ms period), fall_height = 0.
+ * An explicit substep on a mode of stiffness k, damping c and effective mass m_e is stable iff 2 h c / m_e + h^2 k / m_e < 4; the
+ * hardest mode is friction on the foot's own small effective mass (c = mu f_n / v_stiction), which is why neither a stiction speed
+ * of 1e-3 m/s nor a substep of 1 ms can be used here (profiles/r08/ground.md has the sweep).
+ *
+ * Flags, per instance and per step, an int32 bit field:
+ *   WBC_GROUND_SLIP  in some substep a loaded foot (f_n > 0) had |v_t| > v_stiction;
+ *   WBC_GROUND_FELL  the trunk origin is at or below fall_height at the end of the step (forward: in the given state);
+ *   WBC_GROUND_CLIP  some |tau_k| > tau_max (1 + 1e-9) (clipping itself is always applied);
+ *   WBC_GROUND_BAD   not answerable: a non-finite value in q, v, tau or ext_wrench, a mu_p or s_p that is not positive and finite, or
+ *                    a non-finite result in any substep.  q and v are left bit-for-bit untouched, force, vdot and contact are 0, and
+ *                    of the other bits only CLIP is reported.
+ *
+ * Conventions of wbc.h: SoA with the batch index fastest (row r of instance i at base[r*ld + i]); device pointers only; n <= WBC_MAX_LD,
+ * ld >= n; every pointer not named as required may be NULL; 0 on success, < 0 on misuse or a HIP error with the message in
+ * wbc_last_error(); nothing throws; every call leaves the calling thread's current HIP device as it found it.  Asynchronous on
+ * `hip_stream` (NULL = the default stream).
+ */
+#ifndef WBC_GROUND_H
+#define WBC_GROUND_H
+
+#include <stdint.h>
+#include "wbc.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define WBC_GROUND_SLIP 1
+#define WBC_GROUND_FELL 2
+#define WBC_GROUND_CLIP 4
+#define WBC_GROUND_BAD 8
+
+typedef struct {
+  double stiffness;    /* k  [N/m] */
+  double dissipation;  /* d  [s/m] */
+  double mu;           /* mu_p where no per-instance value is given */
+  double v_stiction;   /* v_s  [m/s] */
+  double foot_radius;  /* [m] */
+  double tau_max;      /* actuator limit [N m] */
+  double max_substep;  /* longest explicit substep [s] */
+  double fall_height;  /* FELL: trunk origin at or below this height [m] */
+} wbc_ground_params;
+typedef struct wbc_ground_s* wbc_ground;
+
+/* The defaults for `model` (stiffness and dissipation depend on its weight and gravity). */
+int wbc_ground_params_default(const wbc_model* model, wbc_ground_params* out);
+/* params NULL = defaults.  The model's joint axes must follow the pattern wbc_create accepts. */
+int wbc_ground_create(const wbc_model* model, const wbc_ground_params* params, int device, wbc_ground* out);
+int wbc_ground_destroy(wbc_ground g);
+
+/* One force evaluation, no state change.  Required: q [19][ld], v [18][ld], tau [12][ld] (actuator order, as wbc_step writes them).
+ * Optional: mu [n] (default params.mu), mass_scale [n] (default 1.0), ext_wrench [6][ld] (default 0), and the outputs vdot [18][ld]
+ * (rows in the order of v), force [12][ld] (world frame, ground on foot, row 3*foot + xyz, feet [LF RF LH RH]), contact [n] (bit c:
+ * foot c has phi > 0) and flags [n]. */
+int wbc_ground_forward(wbc_ground g, void* hip_stream, int n, int ld, const double* q, const double* v, const double* tau,
+                       const double* mu, const double* mass_scale, const double* ext_wrench, double* vdot, double* force,
+                       uint8_t* contact, int32_t* flags);
+/* One control period dt > 0 in S substeps, in place on q and v; time [n] (optional) += dt.  force: the mean over the substeps
+ * (impulse / dt); contact: of the last substep; counts [4][ld] (optional, zeroed by the caller): row b += 1 for every step that raises
+ * flag bit b. */
+int wbc_ground_step(wbc_ground g, void* hip_stream, int n, int ld, double dt, double* q, double* v, double* time, const double* tau,
+                    const double* mu, const double* mass_scale, const double* ext_wrench, double* force, uint8_t* contact,
+                    int32_t* flags, int32_t* counts);
+/* Closed loop: `steps` x (wbc_traj_lookup -> wbc_step(h) -> wbc_ground_step), all on hip_stream (h is bound to it as wbc_set_stream
+ * does).  WBC_DEVICE_PTRS handles only; h and g on the same device.  The controller gets the schedule's contact_mask; the ground
+ * decides what actually touches.  mu / mass_scale go to the controller, ground_mu / ground_mass_scale / ext_wrench to the plant.
+ * Required: q, v, time, targets [54][ld], contact_mask [n], tau [12][ld].  The controller's statistics accumulate in h as they do in
+ * wbc_rollout; on return targets / contact_mask / tau / metrics / status / force / contact / flags hold the last tick's values. */
+int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stream, int steps, double dt, int n, int ld, double* q,
+                       double* v, double* time, double* targets, uint8_t* contact_mask, const double* mu, const double* mass_scale,
+                       const double* ground_mu, const double* ground_mass_scale, const double* ext_wrench, double* tau,
+                       double* metrics, int32_t* status, double* force, uint8_t* contact, int32_t* flags, int32_t* counts);
+/* Registers, scratch bytes per lane, LDS bytes and threads per block of the ground-step kernel. */
+int wbc_ground_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

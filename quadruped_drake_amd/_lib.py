@@ -13,7 +13,7 @@ c_i32_p = C.POINTER(C.c_int32)
 KIND_ID, KIND_MPTC, KIND_PC, KIND_CLF = 0, 1, 2, 3
 DEVICE_PTRS, HOST_PTRS = 0, 1
 
-# every symbol include/wbc.h (the controller interface), include/wbc_plant.h (the plant step; prototypes in plant.py) and
+# every symbol include/wbc.h (the controller interface), include/wbc_plant.h and include/wbc_ground.h (the plant steps; prototypes in plant.py) and
 # include/wbc_extras.h (frozen out-of-scope exports) declare
 SYMBOLS = ["wbc_last_error", "wbc_version", "wbc_params_default", "wbc_create", "wbc_destroy", "wbc_set_stream",
            "wbc_step", "wbc_sync", "wbc_time_steps", "wbc_time_steps_result", "wbc_time_steps_each", "wbc_stats_get", "wbc_stats_reset", "wbc_stats_pack", "wbc_stats_reduce", "wbc_set_variant", "wbc_set_warm_start", "wbc_set_vdot_output", "wbc_integrate", "wbc_rollout",
@@ -21,7 +21,9 @@ SYMBOLS = ["wbc_last_error", "wbc_version", "wbc_params_default", "wbc_create", 
            "wbc_traj_destroy", "wbc_traj_lookup", "wbc_robot_state_decode", "wbc_robot_state_encode",
            "wbc_robot_states_unpack", "wbc_robot_controls_pack", "wbc_pd_step",
            "wbc_plant_params_default", "wbc_plant_create", "wbc_plant_destroy", "wbc_plant_forward", "wbc_plant_step", "wbc_plant_rollout",
-           "wbc_plant_kernel_info"]
+           "wbc_plant_kernel_info",
+           "wbc_ground_params_default", "wbc_ground_create", "wbc_ground_destroy", "wbc_ground_forward", "wbc_ground_step",
+           "wbc_ground_rollout", "wbc_ground_kernel_info"]
 
 
 class WbcModel(C.Structure):

@@ -5,6 +5,10 @@ instead applies the controller's torques to a robot of its own -- the same kinem
 and actuator limit -- holds the stance feet with rigid contacts and reports, per instance and step, where a real ground would have
 let go (PULL, CONE), where a torque was clipped (CLIP) and what it could not answer (BAD).  `closed_loop` chains
 lookup -> controller tick -> plant step on the device.  Torch tensors and torch's current stream, as in controller.py.
+
+`GroundContactPlant` (include/wbc_ground.h) has a ground instead of held feet: a compliant half-space z = 0 whose force on each
+foot is an explicit function of the state, so feet lift off, land and slip and a robot that tips falls.  One `step` runs all
+explicit substeps of a control period in a single launch.  `closed_loop` takes either plant.
 """
 import ctypes as C
 import math
@@ -15,10 +19,16 @@ from . import _lib
 from .controller import load_model
 
 PULL, CONE, CLIP, BAD = 1, 2, 4, 8
+SLIP, FELL = 1, 2   # GroundContactPlant's bits 0 and 1 (CLIP and BAD as above)
 
 
 class WbcPlantParams(C.Structure):
     _fields_ = [("Kd_contact", C.c_double), ("tau_max", C.c_double), ("mu", C.c_double)]
+
+
+class WbcGroundParams(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("stiffness", "dissipation", "mu", "v_stiction", "foot_radius", "tau_max", "max_substep",
+                                          "fall_height")]
 
 
 _bound = None
@@ -37,6 +47,14 @@ def _L():
         l.wbc_plant_step.argtypes = [P, P, C.c_int, C.c_int, C.c_double] + [P] * 11
         l.wbc_plant_rollout.argtypes = [P, P, P, P, C.c_int, C.c_double, C.c_int, C.c_int] + [P] * 15
         l.wbc_plant_kernel_info.argtypes = [P] + [C.POINTER(C.c_int)] * 4
+        G = C.POINTER(WbcGroundParams)
+        l.wbc_ground_params_default.argtypes = [C.POINTER(_lib.WbcModel), G]
+        l.wbc_ground_create.argtypes = [C.POINTER(_lib.WbcModel), G, C.c_int, C.POINTER(C.c_void_p)]
+        l.wbc_ground_destroy.argtypes = [P]
+        l.wbc_ground_forward.argtypes = [P, P, C.c_int, C.c_int] + [P] * 10
+        l.wbc_ground_step.argtypes = [P, P, C.c_int, C.c_int, C.c_double] + [P] * 11
+        l.wbc_ground_rollout.argtypes = [P, P, P, P, C.c_int, C.c_double, C.c_int, C.c_int] + [P] * 17
+        l.wbc_ground_kernel_info.argtypes = [P] + [C.POINTER(C.c_int)] * 4
         _bound = l
     return _bound
 
@@ -142,13 +160,123 @@ class RigidContactPlant:
         return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
 
 
-def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=None, plant_mu=None, plant_mass_scale=None, counts=None):
-    """`steps` x (target lookup at time -> ctrl tick -> plant step) on the device (wbc_plant_rollout), on torch's current stream.
-    Updates q, v, time in place; counts (int32 [4, N], optional) accumulates the plant's flag bits.  mu / mass_scale go to the
-    controller, plant_mu / plant_mass_scale to the plant.  Returns the last tick's (tau, metrics, status, targets, mask, force, flags)."""
+def _wbc_model(table, q_perm, act_perm):
+    m = _lib.WbcModel()
+    flat = np.asarray(table["flat"], dtype=np.float64)
+    assert flat.size == 215
+    m.flat[:] = flat.tolist()
+    m.q_perm[:] = list(range(12)) if q_perm is None else [int(x) for x in q_perm]
+    m.act_perm[:] = [int(x) for x in (table.get("act_perm", range(12)) if act_perm is None else act_perm)]
+    return m
+
+
+class GroundContactPlant:
+    """Forward dynamics of N robots under applied torques on a compliant half-space z = 0 (include/wbc_ground.h): Hunt-Crossley
+    normal force, Coulomb friction regularised below v_stiction, explicit substeps of at most max_substep inside one launch.
+
+    model, q_perm, act_perm as RigidContactPlant.  Every parameter left None takes the model's default (wbc_ground_params_default:
+    stiffness = weight / 1 mm, dissipation = 1 / sqrt(g 1 mm), mu 1.0, v_stiction 0.05 m/s, foot_radius 0, tau_max inf,
+    max_substep 0.0625 ms, fall_height 0).  Below v_stiction a loaded foot creeps at up to v_stiction."""
+
+    def __init__(self, model="mini_cheetah", device=0, stiffness=None, dissipation=None, mu=None, v_stiction=None, foot_radius=None,
+                 tau_max=None, max_substep=None, fall_height=None, q_perm=None, act_perm=None):
+        self.table = load_model(model) if isinstance(model, str) else model
+        self.device = int(device)
+        L = _L()
+        m = _wbc_model(self.table, q_perm, act_perm)
+        p = WbcGroundParams()
+        _lib.check(L.wbc_ground_params_default(C.byref(m), C.byref(p)))
+        for k, x in (("stiffness", stiffness), ("dissipation", dissipation), ("mu", mu), ("v_stiction", v_stiction),
+                     ("foot_radius", foot_radius), ("tau_max", tau_max), ("max_substep", max_substep), ("fall_height", fall_height)):
+            if x is not None:
+                setattr(p, k, float(x))
+        self.params = p
+        h = C.c_void_p()
+        _lib.check(L.wbc_ground_create(C.byref(m), C.byref(p), self.device, C.byref(h)))
+        self._h = h
+        self._L = L
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.wbc_ground_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def substeps(self, dt):
+        """The number of explicit substeps wbc_ground_step takes for a period dt."""
+        return max(1, int(math.ceil(float(dt) / self.params.max_substep * (1.0 - 1e-12))))
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _inputs(self, q, v, tau, mu, mass_scale, ext_wrench):
+        import torch
+        n = int(q.shape[1])
+        d = self.device
+        return n, [_dev_ptr(q, 19, n, torch.float64, "q", d), _dev_ptr(v, 18, n, torch.float64, "v", d),
+                   _dev_ptr(tau, 12, n, torch.float64, "tau", d), _dev_ptr(mu, 0, n, torch.float64, "mu", d, True),
+                   _dev_ptr(mass_scale, 0, n, torch.float64, "mass_scale", d, True),
+                   _dev_ptr(ext_wrench, 6, n, torch.float64, "ext_wrench", d, True)]
+
+    def forward(self, q, v, tau, mu=None, mass_scale=None, ext_wrench=None):
+        """One force evaluation -> (vdot[18, N], force[12, N], contact[N] uint8 foot bits, flags[N]); q and v are not changed.
+        Asynchronous on torch's current stream."""
+        import torch
+        n, ins = self._inputs(q, v, tau, mu, mass_scale, ext_wrench)
+        dev = "cuda:%d" % self.device
+        vd = torch.empty((18, n), dtype=torch.float64, device=dev); f = torch.empty((12, n), dtype=torch.float64, device=dev)
+        ct = torch.empty((n,), dtype=torch.uint8, device=dev); fl = torch.empty((n,), dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _lib.check(self._L.wbc_ground_forward(self._h, self._stream(), n, n, *ins, p(vd), p(f), p(ct), p(fl)))
+        return vd, f, ct, fl
+
+    def step(self, q, v, tau, dt, time=None, mu=None, mass_scale=None, ext_wrench=None, counts=None, out=None):
+        """One control period dt in substeps(dt) explicit substeps, in place on q, v (time += dt when given; counts[4, N] int32:
+        row b += 1 when flag bit b is raised).  -> (force[12, N] mean over the substeps, contact[N] of the last substep, flags[N]);
+        out: such a triple to write into."""
+        import torch
+        n, ins = self._inputs(q, v, tau, mu, mass_scale, ext_wrench)
+        d = self.device
+        dev = "cuda:%d" % d
+        if out is None:
+            out = (torch.empty((12, n), dtype=torch.float64, device=dev), torch.empty((n,), dtype=torch.uint8, device=dev),
+                   torch.empty((n,), dtype=torch.int32, device=dev))
+        f, ct, fl = out
+        pt = _dev_ptr(time, 0, n, torch.float64, "time", d, True)
+        pc = _dev_ptr(counts, 4, n, torch.int32, "counts", d, True)
+        outs = [_dev_ptr(f, 12, n, torch.float64, "force", d), _dev_ptr(ct, 0, n, torch.uint8, "contact", d),
+                _dev_ptr(fl, 0, n, torch.int32, "flags", d)]
+        _lib.check(self._L.wbc_ground_step(self._h, self._stream(), n, n, float(dt), ins[0], ins[1], pt, *ins[2:], *outs, pc))
+        return f, ct, fl
+
+    def kernel_info(self):
+        """Registers, scratch bytes per lane, LDS bytes and threads per block of the ground-step kernel."""
+        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self._L.wbc_ground_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
+
+
+def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=None, plant_mu=None, plant_mass_scale=None, counts=None,
+                ext_wrench=None):
+    """`steps` x (target lookup at time -> ctrl tick -> plant step) on the device, on torch's current stream: wbc_plant_rollout for
+    a RigidContactPlant, wbc_ground_rollout for a GroundContactPlant.  Updates q, v, time in place; counts (int32 [4, N], optional)
+    accumulates the plant's flag bits.  mu / mass_scale go to the controller, plant_mu / plant_mass_scale to the plant.
+    ext_wrench ([6, N], GroundContactPlant only): a world-frame wrench on the trunk held over the whole loop.
+    Returns the last tick's (tau, metrics, status, targets, mask, force, flags), and for a GroundContactPlant also contact."""
     import torch
     if ctrl.host_ptrs:
         raise ValueError("closed_loop: needs a device-pointer controller")
+    ground = isinstance(plant, GroundContactPlant)
+    if not ground and not isinstance(plant, RigidContactPlant):
+        raise TypeError("closed_loop: plant must be a RigidContactPlant or a GroundContactPlant")
+    if ext_wrench is not None and not ground:
+        raise ValueError("closed_loop: ext_wrench needs a GroundContactPlant")
     n = int(q.shape[1])
     d = plant.device
     ptr = lambda a, rows, dt_, name, opt=False: _dev_ptr(a, rows, n, dt_, name, d, opt)
@@ -156,6 +284,7 @@ def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=No
     pmu, pms = ptr(mu, 0, torch.float64, "mu", True), ptr(mass_scale, 0, torch.float64, "mass_scale", True)
     ppmu, ppms = ptr(plant_mu, 0, torch.float64, "plant_mu", True), ptr(plant_mass_scale, 0, torch.float64, "plant_mass_scale", True)
     pc = ptr(counts, 4, torch.int32, "counts", True)
+    pw = ptr(ext_wrench, 6, torch.float64, "ext_wrench", True)
     dev = q.device
     tg = torch.empty((54, n), dtype=torch.float64, device=dev); mk = torch.empty((n,), dtype=torch.uint8, device=dev)
     tau = torch.empty((12, n), dtype=torch.float64, device=dev); met = torch.empty((4, n), dtype=torch.float64, device=dev)
@@ -163,6 +292,13 @@ def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=No
     f = torch.zeros((12, n), dtype=torch.float64, device=dev); fl = torch.zeros((n,), dtype=torch.int32, device=dev)
     p = lambda t: C.c_void_p(t.data_ptr())
     s = torch.cuda.current_stream(d).cuda_stream
+    if ground:
+        ct = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        _lib.check(plant._L.wbc_ground_rollout(ctrl._h, plant._h, traj._h, C.c_void_p(s), int(steps), float(dt), n, n, pq, pv, pt, p(tg),
+                                               p(mk), pmu, pms, ppmu, ppms, pw, p(tau), p(met), p(st), p(f), p(ct), p(fl), pc))
+        ctrl._bound_stream = s
+        ctrl._keep = (tg, mk, tau, met, st, f, fl, ct, mu, mass_scale, plant_mu, plant_mass_scale, ext_wrench)
+        return tau, met, st, tg, mk, f, fl, ct
     _lib.check(plant._L.wbc_plant_rollout(ctrl._h, plant._h, traj._h, C.c_void_p(s), int(steps), float(dt), n, n, pq, pv, pt, p(tg),
                                           p(mk), pmu, pms, ppmu, ppms, p(tau), p(met), p(st), p(f), p(fl), pc))
     ctrl._bound_stream = s   # wbc_plant_rollout bound the controller to this stream (wbc_set_stream)

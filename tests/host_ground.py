@@ -1,0 +1,67 @@
+"""ctypes view of tools/libhost_ground.so: the compliant-ground plant math of csrc/wbc_ground.hpp instantiated on the host
+(tests only)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_LIB = None
+PARAM_NAMES = ("stiffness", "dissipation", "mu", "v_stiction", "foot_radius", "tau_max", "max_substep", "fall_height")
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        so = os.path.join(_ROOT, "tools", "libhost_ground.so")
+        srcs = [os.path.join(_ROOT, "tools", "host_ground.cpp")] + [
+            os.path.join(_ROOT, "quadruped_drake_amd", "csrc", f) for f in ("wbc_ground.hpp", "wbc_plant.hpp", "wbc_tick.hpp", "wbc_model.hpp")]
+        if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(s) for s in srcs):
+            subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-ffp-contract=off", "-o", so, srcs[0]])
+        _LIB = C.CDLL(so)
+        _LIB.host_ground_defaults.argtypes = [C.c_void_p, C.c_void_p]
+        _LIB.host_ground_batch.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 12)
+    return _LIB
+
+
+def _p(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def defaults(flat):
+    """The default parameters of a model as a dict keyed by PARAM_NAMES."""
+    flat = np.ascontiguousarray(flat, dtype=np.float64)
+    out = np.zeros(8)
+    assert lib().host_ground_defaults(_p(flat), _p(out)) == 0
+    return dict(zip(PARAM_NAMES, out.tolist()))
+
+
+def run(flat, q, v, tau, mu=None, mass_scale=None, ext_wrench=None, params=None, q_perm=None, act_perm=None, dt=None, substeps=0,
+        time=None, counts=None):
+    """One force evaluation (dt None) or one step of `substeps` substeps (0: ceil(dt / max_substep)).  params: a dict overriding
+    defaults(flat).  Returns dict(vdot, force, contact, flags[, q, v, time, counts, substeps]) -- copies, inputs untouched."""
+    q = np.array(q, dtype=np.float64, order="C"); v = np.array(v, dtype=np.float64, order="C")
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    n = q.shape[1]
+    flat = np.ascontiguousarray(flat, dtype=np.float64)
+    qp = np.ascontiguousarray(range(12) if q_perm is None else q_perm, dtype=np.int32)
+    ap = np.ascontiguousarray(range(12) if act_perm is None else act_perm, dtype=np.int32)
+    pr = None
+    if params is not None:
+        d = defaults(flat); d.update(params)
+        pr = np.array([d[k] for k in PARAM_NAMES], dtype=np.float64)
+    mu = None if mu is None else np.ascontiguousarray(mu, dtype=np.float64)
+    ms = None if mass_scale is None else np.ascontiguousarray(mass_scale, dtype=np.float64)
+    we = None if ext_wrench is None else np.ascontiguousarray(ext_wrench, dtype=np.float64)
+    tm = None if time is None else np.array(time, dtype=np.float64)
+    cn = None if counts is None else np.array(counts, dtype=np.int32)
+    vd = np.zeros((18, n)); f = np.zeros((12, n)); ct = np.zeros(n, np.uint8); fl = np.zeros(n, np.int32)
+    rc = lib().host_ground_batch(_p(flat), _p(qp), _p(ap), _p(pr), n, n, 0 if dt is None else 1, int(substeps),
+                                 0.0 if dt is None else float(dt), _p(q), _p(v), _p(tm), _p(tau), _p(mu), _p(ms), _p(we), _p(vd), _p(f),
+                                 _p(ct), _p(fl), _p(cn))
+    assert rc > 0
+    out = dict(vdot=vd, force=f, contact=ct, flags=fl)
+    if dt is not None:
+        out.update(q=q, v=v, time=tm, counts=cn, substeps=rc)
+    return out
