@@ -38,12 +38,16 @@ def defaults(flat):
 
 
 def run(flat, q, v, tau, mu=None, mass_scale=None, ext_wrench=None, params=None, q_perm=None, act_perm=None, dt=None, substeps=0,
-        time=None, counts=None):
+        time=None, counts=None, n=None, out=None):
     """One force evaluation (dt None) or one step of `substeps` substeps (0: ceil(dt / max_substep)).  params: a dict overriding
-    defaults(flat).  Returns dict(vdot, force, contact, flags[, q, v, time, counts, substeps]) -- copies, inputs untouched."""
+    defaults(flat).  Returns dict(vdot, force, contact, flags[, q, v, time, counts, substeps]) -- copies, inputs untouched.
+    n: the batch size where the arrays are wider (ld = q.shape[1] > n; every 2-D array then has ld columns).  out: a dict of
+    preset vdot / force / contact / flags arrays to write into (for looking at what is left of the padding columns)."""
     q = np.array(q, dtype=np.float64, order="C"); v = np.array(v, dtype=np.float64, order="C")
     tau = np.ascontiguousarray(tau, dtype=np.float64)
-    n = q.shape[1]
+    ld = q.shape[1]
+    n = ld if n is None else int(n)
+    assert 0 < n <= ld
     flat = np.ascontiguousarray(flat, dtype=np.float64)
     qp = np.ascontiguousarray(range(12) if q_perm is None else q_perm, dtype=np.int32)
     ap = np.ascontiguousarray(range(12) if act_perm is None else act_perm, dtype=np.int32)
@@ -56,8 +60,14 @@ def run(flat, q, v, tau, mu=None, mass_scale=None, ext_wrench=None, params=None,
     we = None if ext_wrench is None else np.ascontiguousarray(ext_wrench, dtype=np.float64)
     tm = None if time is None else np.array(time, dtype=np.float64)
     cn = None if counts is None else np.array(counts, dtype=np.int32)
-    vd = np.zeros((18, n)); f = np.zeros((12, n)); ct = np.zeros(n, np.uint8); fl = np.zeros(n, np.int32)
-    rc = lib().host_ground_batch(_p(flat), _p(qp), _p(ap), _p(pr), n, n, 0 if dt is None else 1, int(substeps),
+    vd = np.zeros((18, ld)); f = np.zeros((12, ld)); ct = np.zeros(ld, np.uint8); fl = np.zeros(ld, np.int32)
+    if out is not None:
+        vd, f, ct, fl = out["vdot"], out["force"], out["contact"], out["flags"]
+        assert vd.shape == (18, ld) and f.shape == (12, ld) and vd.dtype == f.dtype == np.float64
+        assert ct.dtype == np.uint8 and fl.dtype == np.int32 and all(a.flags.c_contiguous for a in (vd, f, ct, fl))
+    for a, rows in ((tau, 12), (we, 6), (cn, 4)):
+        assert a is None or a.shape == (rows, ld)
+    rc = lib().host_ground_batch(_p(flat), _p(qp), _p(ap), _p(pr), n, ld, 0 if dt is None else 1, int(substeps),
                                  0.0 if dt is None else float(dt), _p(q), _p(v), _p(tm), _p(tau), _p(mu), _p(ms), _p(we), _p(vd), _p(f),
                                  _p(ct), _p(fl), _p(cn))
     assert rc > 0

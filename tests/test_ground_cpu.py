@@ -10,6 +10,7 @@ import pytest
 import energy_model as em
 import ground_oracle as go
 import host_ground as hg
+import plant_edges as pe
 from quadruped_drake_amd import load_model, workloads
 
 draw, draw_near_stance = go.draw, go.draw_near_stance
@@ -220,3 +221,157 @@ def test_abi_ground_misuse_without_device():
     assert L.wbc_ground_create(C.byref(m), C.byref(p), 0, C.byref(h)) < 0 and "v_stiction" in err()
     m.q_perm[0] = 1
     assert L.wbc_ground_create(C.byref(m), None, 0, C.byref(h)) < 0 and "permutations" in err()
+
+
+# ---- the edges of the ABI on the host instantiation (the device twins: tests/test_plant_edges_gpu.py)
+def _ground_outs(ld):
+    return dict(vdot=pe.wide(np.zeros((18, 0)), ld), force=pe.wide(np.zeros((12, 0)), ld), contact=pe.wide(np.zeros(0, np.uint8), ld),
+                flags=pe.wide(np.zeros(0, np.int32), ld))
+
+
+@pytest.mark.parametrize("cfg,model", MODELS)
+def test_host_ground_renumbered_with_odd_parameters(cfg, model):
+    """Random q_perm and act_perm and a handle whose every parameter differs from its default: the caller's joint rows are
+    permuted, the oracle sees the canonical rows, a table that carries act_perm and the same parameters."""
+    n = 64
+    t, q, v, tau, sp, we = draw(cfg, n, 41)
+    qp, ap = pe.perm_pair(5, avoid=t.get("act_perm", range(12)))
+    over = pe.odd_ground_params(t, q)
+    q2, v2 = pe.permute_rows(q, v, qp)
+    out = hg.run(t["flat"], q2, v2, tau, mass_scale=sp, ext_wrench=we, params=over, q_perm=qp, act_perm=ap)
+    vd = pe.canonical_v(out["vdot"], qp)
+    t2, P = pe.table_with(t, ap), go.params(t, over)
+    worst = 0.0
+    for backend in BACKENDS:
+        vdo, fo, cto, flo = go.forward(t2, q, v, tau, mass_scale=sp, ext_wrench=we, P=P, backend=backend)
+        worst = max(worst, _rel(vd, vdo), _rel(out["force"], fo))
+        assert _rel(vd, vdo) < 1e-9 and _rel(out["force"], fo) < 1e-9, backend
+        assert np.array_equal(out["contact"], cto), backend
+        keep = pe.ground_margin_keep(t2, q, v, tau, sp, P, backend)
+        assert keep.sum() >= 0.9 * n, backend
+        assert np.array_equal(out["flags"][keep], flo[keep]), backend
+        for bit in (go.SLIP, go.FELL, go.CLIP):
+            assert ((flo & bit) != 0).any() and ((flo & bit) == 0).any(), (backend, bit)
+        # the clipped answer differs from the unclipped one exactly where CLIP is set
+        vdu = go.forward(t2, q, v, tau, mass_scale=sp, ext_wrench=we, P=go.params(t, dict(over, tau_max=np.inf)), backend=backend)[0]
+        clip = (flo & go.CLIP) != 0
+        assert (np.abs(vdu - vdo)[:, clip].max(0) > 1e-3).all() and np.array_equal(vdu[:, ~clip], vdo[:, ~clip])
+    print("renumbered forward", model, "worst", worst)
+    # the same launch under the identity numbering: bit for bit after un-permuting
+    ident = hg.run(t["flat"], q, v, pe.tau_for_identity(tau, ap), mass_scale=sp, ext_wrench=we, params=over)
+    assert pe.same_bits(vd, ident["vdot"]) and pe.same_bits(out["force"], ident["force"])
+    assert np.array_equal(out["flags"], ident["flags"])
+
+
+@pytest.mark.parametrize("S,dt", pe.substep_cases())
+@pytest.mark.parametrize("model", ["mini_cheetah", "anymal_b"])
+def test_host_ground_renumbered_step_at_every_substep_count(model, S, dt):
+    n = 16
+    t, q, v, tau, sp, we = draw_near_stance(model, n, 43)
+    qp, ap = pe.perm_pair(6, avoid=t.get("act_perm", range(12)))
+    over = dict(pe.odd_ground_params(t, q), tau_max=9.5, fall_height=0.0)
+    q2, v2 = pe.permute_rows(q, v, qp)
+    out = hg.run(t["flat"], q2, v2, tau, mass_scale=sp, ext_wrench=we, params=over, q_perm=qp, act_perm=ap, dt=dt)
+    assert out["substeps"] == S == go.substeps(dt, go.params(t, over)["max_substep"])
+    qh, vh = pe.canonical_q(out["q"], qp), pe.canonical_v(out["v"], qp)
+    for backend in BACKENDS:
+        qn, vn, fm, ct, fl = go.step(pe.table_with(t, ap), q, v, tau, dt, S, mass_scale=sp, ext_wrench=we, P=go.params(t, over),
+                                     backend=backend)
+        print("renumbered step", model, S, backend, _rel(qh, qn), _rel(vh, vn), _rel(out["force"], fm))
+        assert _rel(qh, qn) < 1e-9 and _rel(vh, vn) < 1e-9 and _rel(out["force"], fm) < 1e-9, backend
+        assert np.array_equal(out["contact"], ct) and np.array_equal(out["flags"], fl), backend
+        assert ((fl & go.CLIP) != 0).any() and ((fl & go.CLIP) == 0).any()
+
+
+@pytest.mark.parametrize("n", [1, 17, 203])
+def test_host_ground_wide_arrays_and_batch_tails(n):
+    """ld > n on the host tool: the columns below n equal the ld = n run bit for bit and the padding keeps its bits."""
+    t, b = pe.ground_batch("anymal_b", 203, 11)
+    ap = t.get("act_perm")
+    cut = {k: np.ascontiguousarray(x[..., :n]) for k, x in b.items()}
+    time, counts = np.linspace(0.0, 1.0, 203)[:n], (np.arange(4 * 203).reshape(4, 203) % 3).astype(np.int32)[:, :n]
+    full = {}
+    for dt in (None, 1e-3):
+        kw = dict(mu=cut["mu"], mass_scale=cut["mass_scale"], ext_wrench=cut["ext_wrench"], act_perm=ap, dt=dt)
+        if dt:
+            kw.update(time=time, counts=counts)
+        base = hg.run(t["flat"], cut["q"], cut["v"], cut["tau"], **kw)
+        assert (base["flags"] & go.BAD == 0).all()
+        for ld in (n + 5, 256):
+            nan = lambda a: pe.wide(a, ld, np.nan)
+            st = (lambda a: pe.wide(a, ld)) if dt else nan            # q and v: inputs of forward, in place in step
+            kw2 = dict(mu=nan(cut["mu"]), mass_scale=nan(cut["mass_scale"]), ext_wrench=nan(cut["ext_wrench"]), act_perm=ap, dt=dt, n=n,
+                       out=_ground_outs(ld))
+            if dt:
+                kw2.update(time=pe.wide(time, ld), counts=pe.wide(counts, ld))
+            got = hg.run(t["flat"], st(cut["q"]), st(cut["v"]), nan(cut["tau"]), **kw2)
+            for k, x in base.items():
+                if isinstance(x, np.ndarray) and not (dt and k == "vdot"):
+                    assert pe.same_bits(got[k][..., :n], x), (k, ld)
+                    assert pe.padding_kept(got[k], n, None if (dt or k not in ("q", "v")) else np.nan), (k, ld)
+        full[dt] = base
+    if n < 203:      # the dead quads compute on robot n - 1: nothing of it may leak into the answer of the others
+        kw = dict(mu=b["mu"], mass_scale=b["mass_scale"], ext_wrench=b["ext_wrench"], act_perm=ap)
+        big = hg.run(t["flat"], b["q"], b["v"], b["tau"], **kw)
+        assert all(pe.same_bits(big[k][..., :n], full[None][k]) for k in ("vdot", "force", "contact", "flags"))
+        big = hg.run(t["flat"], b["q"], b["v"], b["tau"], dt=1e-3, **kw)
+        assert all(pe.same_bits(big[k][..., :n], full[1e-3][k]) for k in ("q", "v", "force", "contact", "flags"))
+
+
+def _ground_poison_run(t, b, dt, tau_max, S=None):
+    kw = dict(mu=b["mu"], mass_scale=b["mass_scale"], ext_wrench=b["ext_wrench"], act_perm=t.get("act_perm"), params={"tau_max": tau_max})
+    if dt is None:
+        return hg.run(t["flat"], b["q"], b["v"], b["tau"], **kw)
+    return hg.run(t["flat"], b["q"], b["v"], b["tau"], dt=dt, time=b["time"], counts=b["counts"], **kw)
+
+
+@pytest.mark.parametrize("model", ["mini_cheetah", "anymal_b"])
+def test_host_ground_malformed_kinds(model):
+    """Every entry of pe.plant_poisons through the host forward and step: the damaged instances are BAD (with CLIP where a torque
+    is over the limit, and nothing else), zeroed and untouched; everyone else keeps their bits; the oracle flags alike."""
+    n, dt, tm = 80, 1e-3, 25.0
+    t, base = pe.ground_batch(model, n, 17)
+    base["time"] = np.linspace(0.0, 1.0, n); base["counts"] = (np.arange(4 * n).reshape(4, n) % 5).astype(np.int32)
+    clean = {d: _ground_poison_run(t, base, d, tm) for d in (None, dt)}
+    P = go.params(t, {"tau_max": tm})
+    for j, (name, (damage, want)) in enumerate(pe.plant_poisons(t.get("act_perm", range(12)), True, 40.0).items()):
+        b = pe.copy_batch(base)
+        hit = pe.slots_of(j, n)
+        for i in hit:
+            damage(b, i)
+        ok = np.ones(n, bool); ok[hit] = False
+        for d in (None, dt):
+            out = _ground_poison_run(t, b, d, tm)
+            for k, x in clean[d].items():
+                if isinstance(x, np.ndarray):
+                    assert pe.same_bits(out[k][..., ok], x[..., ok]), (name, d, k)
+            if want == "legal":
+                assert (out["flags"][hit] & go.BAD == 0).all(), name
+                with np.errstate(all="ignore"):
+                    if d is None:
+                        vdo, fo, cto, flo = go.forward(t, b["q"], b["v"], b["tau"], b["mu"], b["mass_scale"], b["ext_wrench"], P, idx=hit)
+                        assert _rel(out["vdot"][:, hit], vdo) < 1e-9 and _rel(out["force"][:, hit], fo) < 1e-9
+                    else:
+                        sel = lambda a: a[..., hit]
+                        qn, vn, fm, cto, flo = go.step(t, sel(b["q"]), sel(b["v"]), sel(b["tau"]), d, 16, sel(b["mu"]), sel(b["mass_scale"]),
+                                                       sel(b["ext_wrench"]), P)
+                        assert _rel(out["q"][:, hit], qn) < 1e-9 and _rel(out["v"][:, hit], vn) < 1e-9 and _rel(out["force"][:, hit], fm) < 1e-9
+                assert np.array_equal(out["contact"][hit], cto) and np.array_equal(out["flags"][hit], flo), name
+                continue
+            flags = go.BAD | (go.CLIP if want == "clip_bad" else 0)
+            assert (out["flags"][hit] == flags).all(), (name, d, out["flags"][hit])
+            assert (out["force"][:, hit] == 0).all() and (out["vdot"][:, hit] == 0).all() and (out["contact"][hit] == 0).all(), name
+            with np.errstate(all="ignore"):
+                sel = lambda a: a[..., hit[:2]]
+                if d is None:
+                    flo = go.forward(t, b["q"], b["v"], b["tau"], b["mu"], b["mass_scale"], b["ext_wrench"], P, idx=hit[:2])[3]
+                else:
+                    flo = go.step(t, sel(b["q"]), sel(b["v"]), sel(b["tau"]), d, 16, sel(b["mu"]), sel(b["mass_scale"]), sel(b["ext_wrench"]), P)[4]
+            assert (flo == flags).all(), (name, d, flo)
+            if d is not None:
+                assert pe.same_bits(out["q"][:, hit], b["q"][:, hit]) and pe.same_bits(out["v"][:, hit], b["v"][:, hit]), name
+                want_counts = base["counts"][:, hit].copy()
+                want_counts[3] += 1
+                want_counts[2] += 1 if want == "clip_bad" else 0
+                assert np.array_equal(out["counts"][:, hit], want_counts), name
+                assert np.array_equal(out["time"][hit], base["time"][hit] + d), name

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import host_plant as hp
+import plant_edges as pe
 import plant_oracle as po
 from quadruped_drake_amd import load_model, workloads
 
@@ -137,3 +138,117 @@ def test_abi_plant_misuse_without_device():
     assert L.wbc_plant_params_default(C.byref(p)) == 0
     assert (p.Kd_contact, p.tau_max, p.mu) == (100.0, float("inf"), 1.0)
     assert L.wbc_plant_destroy(None) == 0
+
+
+# ---- the edges of the ABI on the host instantiation (the device twins: tests/test_plant_edges_gpu.py)
+ODD3 = [37.0, 28.0, 0.45]          # Kd_contact, tau_max, mu: each differs from its default (100, inf, 1.0)
+
+
+@pytest.mark.parametrize("cfg,model", [(2, "mini_cheetah")] + MODELS)
+def test_host_plant_renumbered_with_odd_parameters(cfg, model):
+    """Random q_perm and act_perm and a handle whose three parameters differ from their defaults (no per-instance mu: the handle's
+    is used): forward and one step against the dense plant on the canonical rows with a table that carries act_perm."""
+    n = 64
+    b, tau, mask, sp = _draw(cfg, n, 41)
+    t = load_model(model)
+    qp, ap = pe.perm_pair(5, avoid=t.get("act_perm", range(12)))
+    q2, v2 = pe.permute_rows(b["q"], b["v"], qp)
+    t2 = pe.table_with(t, ap)
+    kw = dict(mass_scale=sp, kd=ODD3[0], tau_max=ODD3[1], mu0=ODD3[2])
+    out = hp.run(t["flat"], q2, v2, tau, mask, mass_scale=sp, params3=ODD3, q_perm=qp, act_perm=ap)
+    st = hp.run(t["flat"], q2, v2, tau, mask, mass_scale=sp, params3=ODD3, q_perm=qp, act_perm=ap, dt=2e-3)
+    vdh = pe.canonical_v(out["vdot"], qp)
+    for backend in BACKENDS:
+        vd, f, fl = po.forward(t2, b["q"], b["v"], tau, mask, backend=backend, **kw)
+        print("renumbered rigid", model, backend, _rel(vdh, vd), _rel(out["force"], f))
+        assert _rel(vdh, vd) < 1e-9 and _rel(out["force"], f) < 1e-9, backend
+        keep = np.array([po.margin(t2, b["q"][:, i], b["v"][:, i], tau[:, i], int(mask[i]), ODD3[2], sp[i], ODD3[0], ODD3[1], backend) > 1e-6
+                         for i in range(n)])
+        assert keep.sum() >= 0.9 * n, backend
+        assert np.array_equal(out["flags"][keep], fl[keep]), backend
+        for bit in (po.PULL | po.CONE, po.CLIP):
+            assert ((fl & bit) != 0).any() and ((fl & bit) == 0).any(), (backend, bit)
+        qn, vn, vd, f, fl = po.step(t2, b["q"], b["v"], tau, mask, 2e-3, backend=backend, **kw)
+        assert _rel(pe.canonical_q(st["q"], qp), qn) < 1e-9 and _rel(pe.canonical_v(st["v"], qp), vn) < 1e-9, backend
+        # each parameter matters: the dense plant at the default differs
+        for k, x in (("kd", 100.0), ("tau_max", np.inf)):
+            assert _rel(po.forward(t2, b["q"], b["v"], tau, mask, backend=backend, **dict(kw, **{k: x}))[0], vd) > 1e-3, k
+        assert not np.array_equal(po.forward(t2, b["q"], b["v"], tau, mask, backend=backend, **dict(kw, mu0=1.0))[2], fl)
+    ident = hp.run(t["flat"], b["q"], b["v"], pe.tau_for_identity(tau, ap), mask, mass_scale=sp, params3=ODD3)
+    assert pe.same_bits(vdh, ident["vdot"]) and pe.same_bits(out["force"], ident["force"]) and np.array_equal(out["flags"], ident["flags"])
+
+
+@pytest.mark.parametrize("n", [1, 17, 203])
+def test_host_plant_wide_arrays_and_batch_tails(n):
+    """ld > n on the host tool: the columns below n equal the ld = n run bit for bit and the padding keeps its bits."""
+    t, b = pe.rigid_batch(4, 203, 11)
+    ap = t.get("act_perm")
+    cut = {k: np.ascontiguousarray(x[..., :n]) for k, x in b.items()}
+    time, counts = np.linspace(0.0, 1.0, 203)[:n], (np.arange(4 * 203).reshape(4, 203) % 3).astype(np.int32)[:, :n]
+    for dt in (None, 1e-3):
+        kw = dict(mu=cut["mu"], mass_scale=cut["mass_scale"], act_perm=ap, dt=dt)
+        if dt:
+            kw.update(time=time, counts=counts)
+        base = hp.run(t["flat"], cut["q"], cut["v"], cut["tau"], cut["mask"], **kw)
+        assert (base["flags"] & po.BAD == 0).all()
+        big = hp.run(t["flat"], b["q"], b["v"], b["tau"], b["mask"], mu=b["mu"], mass_scale=b["mass_scale"], act_perm=ap, dt=dt)
+        assert all(pe.same_bits(big[k][..., :n], base[k]) for k in ("vdot", "force", "flags") + (("q", "v") if dt else ()))
+        for ld in (n + 5, 256):
+            nan = lambda a: pe.wide(a, ld, np.nan)
+            st = (lambda a: pe.wide(a, ld)) if dt else nan            # q and v: inputs of forward, in place in step
+            outs = dict(vdot=pe.wide(np.zeros((18, 0)), ld), force=pe.wide(np.zeros((12, 0)), ld), flags=pe.wide(np.zeros(0, np.int32), ld))
+            kw2 = dict(mu=nan(cut["mu"]), mass_scale=nan(cut["mass_scale"]), act_perm=ap, dt=dt, n=n, out=outs)
+            if dt:
+                kw2.update(time=pe.wide(time, ld), counts=pe.wide(counts, ld))
+            got = hp.run(t["flat"], st(cut["q"]), st(cut["v"]), nan(cut["tau"]), pe.wide(cut["mask"], ld), **kw2)
+            for k, x in base.items():
+                if isinstance(x, np.ndarray):
+                    assert pe.same_bits(got[k][..., :n], x), (k, ld)
+                    assert pe.padding_kept(got[k], n, None if (dt or k not in ("q", "v")) else np.nan), (k, ld)
+
+
+@pytest.mark.parametrize("cfg", [3, 4])
+def test_host_plant_malformed_kinds(cfg):
+    """Every entry of pe.plant_poisons through the host forward and step: the damaged instances are BAD (with CLIP where a torque
+    is over the limit, and nothing else), zeroed and untouched; everyone else keeps their bits; the dense plant flags alike."""
+    n, dt, tm = 80, 1e-3, 25.0
+    t, base = pe.rigid_batch(cfg, n, 17)
+    base["time"] = np.linspace(0.0, 1.0, n); base["counts"] = (np.arange(4 * n).reshape(4, n) % 5).astype(np.int32)
+
+    def run(b, d):
+        kw = dict(mu=b["mu"], mass_scale=b["mass_scale"], act_perm=t.get("act_perm"), params3=[100.0, tm, 1.0])
+        if d is not None:
+            kw.update(dt=d, time=b["time"], counts=b["counts"])
+        return hp.run(t["flat"], b["q"], b["v"], b["tau"], b["mask"], **kw)
+
+    clean = {d: run(base, d) for d in (None, dt)}
+    for j, (name, (damage, want)) in enumerate(pe.plant_poisons(t.get("act_perm", range(12)), False, 40.0).items()):
+        b = pe.copy_batch(base)
+        hit = pe.slots_of(j, n)
+        for i in hit:
+            damage(b, i)
+        ok = np.ones(n, bool); ok[hit] = False
+        flo = None
+        if name not in ("zero_quat", "tiny_quat", "huge_rate"):   # finite inputs, non-finite inside: the dense KKT solve has no rule for them
+            vdo, fo, flo = po.forward(t, b["q"], b["v"], b["tau"], b["mask"], b["mu"], b["mass_scale"], tau_max=tm, idx=hit)
+        for d in (None, dt):
+            out = run(b, d)
+            for k, x in clean[d].items():
+                if isinstance(x, np.ndarray):
+                    assert pe.same_bits(out[k][..., ok], x[..., ok]), (name, d, k)
+            if want == "legal":
+                assert (out["flags"][hit] & po.BAD == 0).all(), name
+                assert _rel(out["vdot"][:, hit], vdo) < 1e-9 and _rel(out["force"][:, hit], fo) < 1e-9, name
+                continue
+            flags = po.BAD | (po.CLIP if want == "clip_bad" else 0)
+            assert (out["flags"][hit] == flags).all(), (name, d, out["flags"][hit])
+            assert (out["force"][:, hit] == 0).all() and (out["vdot"][:, hit] == 0).all(), name
+            if flo is not None:
+                assert (flo == flags).all(), (name, flo)
+            if d is not None:
+                assert pe.same_bits(out["q"][:, hit], b["q"][:, hit]) and pe.same_bits(out["v"][:, hit], b["v"][:, hit]), name
+                want_counts = base["counts"][:, hit].copy()
+                want_counts[3] += 1
+                want_counts[2] += 1 if want == "clip_bad" else 0
+                assert np.array_equal(out["counts"][:, hit], want_counts), name
+                assert np.array_equal(out["time"][hit], base["time"][hit] + d), name
