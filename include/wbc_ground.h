@@ -27,13 +27,30 @@
  * hardest mode is friction on the foot's own small effective mass (c = mu f_n / v_stiction), which is why neither a stiction speed
  * of 1e-3 m/s nor a substep of 1 ms can be used here (profiles/r08/ground.md has the sweep).
  *
+ * Terrain (wbc_ground_set_terrain; this project's definition too).  A terrain is a height field that varies along ONE horizontal
+ * direction: H(x, y) = scale * h(s) with s = (x - x0) cos(yaw) + (y - y0) sin(yaw), h piecewise linear through nk knots (s_k, h_k),
+ * 1 <= nk <= 8, s_k strictly increasing, h constant outside the knots.  A vertical riser is a steep segment (TOWR's Block makes its
+ * riser over 0.03 m).  A handle holds up to 16 profiles; instance i stands on profile terrain_id[i], scaled by terrain_scale[i].
+ * For a foot at p with velocity pd let j be the segment whose half-open interval [s_j, s_j+1) holds the foot's s, with
+ *   g = scale (h_j+1 - h_j) / (s_j+1 - s_j)   and   n = (-g cos(yaw), -g sin(yaw), 1) / sqrt(1 + g^2)
+ * (g = 0, n = z before the first and from the last knot on).  The force law is the one above, written about n:
+ *   phi = foot_radius - (p_z - H(p_x, p_y)) n_z            (the distance to the segment's plane).   If phi <= 0: f_c = 0, exactly.
+ *   v_n = pd . n,   f_n = stiffness * phi * max(0, 1 - dissipation * v_n),   v_t = pd - v_n n,
+ *   f_c = f_n n - mu_p f_n v_t / max(|v_t|, v_stiction)                          (world frame, as before).
+ * SLIP is the same |v_t| > v_stiction on a loaded foot, FELL becomes "the trunk origin at or below H(q_x, q_y) + fall_height",
+ * contact bit c is phi > 0.  With g = 0 and H = 0 this is the law of the plane.  The integrator, the substeps and the stability
+ * condition are untouched: the stiffness along n is still `stiffness`.  The limits of the model: the contact is first order in the
+ * local plane (a foot near a convex knot feels the plane of the segment under it, extended); the normal jumps at a knot; there are
+ * no overhangs and no contact with a riser's face from the side beyond what the steep segment gives; and the controllers still
+ * assume a level ground -- their friction pyramids stay about world z.
+ *
  * Flags, per instance and per step, an int32 bit field:
  *   WBC_GROUND_SLIP  in some substep a loaded foot (f_n > 0) had |v_t| > v_stiction;
  *   WBC_GROUND_FELL  the trunk origin is at or below fall_height at the end of the step (forward: in the given state);
  *   WBC_GROUND_CLIP  some |tau_k| > tau_max (1 + 1e-9) (clipping itself is always applied);
- *   WBC_GROUND_BAD   not answerable: a non-finite value in q, v, tau or ext_wrench, a mu_p or s_p that is not positive and finite, or
- *                    a non-finite result in any substep.  q and v are left bit-for-bit untouched, force, vdot and contact are 0, and
- *                    of the other bits only CLIP is reported.
+ *   WBC_GROUND_BAD   not answerable: a non-finite value in q, v, tau or ext_wrench, a mu_p or s_p that is not positive and finite, a
+ *                    terrain_id beyond the table or a non-finite terrain_scale, or a non-finite result in any substep.  q and v are
+ *                    left bit-for-bit untouched, force, vdot and contact are 0, and of the other bits only CLIP is reported.
  *
  * Conventions of wbc.h: SoA with the batch index fastest (row r of instance i at base[r*ld + i]); device pointers only; n <= WBC_MAX_LD,
  * ld >= n; every pointer not named as required may be NULL; 0 on success, < 0 on misuse or a HIP error with the message in
@@ -97,6 +114,22 @@ int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stre
                        double* metrics, int32_t* status, double* force, uint8_t* contact, int32_t* flags, int32_t* counts);
 /* Registers, scratch bytes per lane, LDS bytes and threads per block of the ground-step kernel. */
 int wbc_ground_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads);
+
+/* ---- Terrain (the model: the head of this file).  A profile: nk knots (s[k], h[k]), the direction yaw of s and its origin. */
+typedef struct { int nk; double x0, y0, yaw; double s[8]; double h[8]; } wbc_terrain_profile;
+#define WBC_GROUND_MAX_PROFILES 16
+/* Host arithmetic only, no device call: < 0 with the message set when count is outside 1 .. 16, an nk outside 1 .. 8, knots that are
+ * not strictly increasing, or any non-finite number. */
+int wbc_terrain_check(const wbc_terrain_profile* profiles, int count);
+/* Checks and copies the table to the handle's device (synchronising with it) and remembers the per-instance device pointers
+ * terrain_id [n] (NULL: profile 0) and terrain_scale [n] (NULL: 1.0); both must be at least as long as the n of every later call and
+ * stay alive in the caller's hands.  count = 0 or profiles = NULL switches the terrain off again.  wbc_ground_forward, wbc_ground_step
+ * and wbc_ground_rollout of this handle then run on the terrain.  A terrain_id >= count or a non-finite terrain_scale makes the
+ * instance WBC_GROUND_BAD; any finite scale is legal, 0 and negative ones included. */
+int wbc_ground_set_terrain(wbc_ground g, const wbc_terrain_profile* profiles, int count, const uint8_t* terrain_id,
+                           const double* terrain_scale);
+/* wbc_ground_kernel_info of the step kernel that runs while a terrain is set. */
+int wbc_ground_terrain_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads);
 
 #ifdef __cplusplus
 }

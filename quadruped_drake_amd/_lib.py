@@ -23,7 +23,7 @@ SYMBOLS = ["wbc_last_error", "wbc_version", "wbc_params_default", "wbc_create", 
            "wbc_plant_params_default", "wbc_plant_create", "wbc_plant_destroy", "wbc_plant_forward", "wbc_plant_step", "wbc_plant_rollout",
            "wbc_plant_kernel_info",
            "wbc_ground_params_default", "wbc_ground_create", "wbc_ground_destroy", "wbc_ground_forward", "wbc_ground_step",
-           "wbc_ground_rollout", "wbc_ground_kernel_info"]
+           "wbc_ground_rollout", "wbc_ground_kernel_info", "wbc_terrain_check", "wbc_ground_set_terrain", "wbc_ground_terrain_kernel_info"]
 
 
 class WbcModel(C.Structure):

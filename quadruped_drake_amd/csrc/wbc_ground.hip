@@ -55,6 +55,15 @@ struct GroundArgs {
   int32_t* counts;
   double k, d, vs, radius, tau_max, mu0, fall_height;
 };
+// The terrain kernels' own argument: the packed table (wbc::terrain_pack, count x TERRAIN_STRIDE doubles, device memory) and the
+// per-instance choice.  GroundArgs stays as the flat kernels take it.
+struct TerrainArgs {
+  const double* table;
+  const uint8_t* id;
+  const double* scale;
+  int count;
+};
+constexpr int TERRAIN_LDS_DOUBLES = wbc::TERRAIN_MAX_PROFILES * wbc::TERRAIN_STRIDE;   // 5 KB
 
 // quad_perm DPP move of a double: CTRL = p0 | p1 << 2 | p2 << 4 | p3 << 6 (lane j of the quad reads lane p_j)
 template <int CTRL> __device__ __forceinline__ double qmove(double x) {
@@ -76,15 +85,16 @@ __device__ __forceinline__ int qor(int x) {
 
 // One force evaluation at the state in registers: base accelerations (replicated), the own leg's joint accelerations and foot
 // force.  Returns ground_foot_force's bits of the own foot.
+template <bool TERRAIN>
 __device__ __forceinline__ int ground_eval(const wbc::ModelC& m, int l, const wbc::GroundLaw<double>& law, double mu, double s_p,
                                            const double* we, const double* qb, const double* vb, const double* th, const double* qd,
-                                           const double* tau_a, double* vdb, double* vdl, double* f) {
+                                           const double* tau_a, double* vdb, double* vdl, double* f, const double* tab, double tscale) {
   using namespace wbc;
   double R0[9];
   plant_rotation(qb, R0);
   const double w0[3] = {vb[0], vb[1], vb[2]}, v0[3] = {vb[3], vb[4], vb[5]};
   PlantLeg<double> L;
-  const int fb = ground_leg_phase(m, l, R0, w0, v0, qb[6], th, qd, tau_a, law, mu, L, f);
+  const int fb = ground_leg_phase<TERRAIN>(m, l, R0, w0, v0, qb[6], th, qd, tau_a, law, mu, L, f, qb[4], qb[5], tab, tscale);
   double S[27];
   plant_base_share(m, R0, w0, s_p, S);
 #pragma unroll
@@ -96,9 +106,17 @@ __device__ __forceinline__ int ground_eval(const wbc::ModelC& m, int l, const wb
   return fb;
 }
 
-template <bool STEP>
-__device__ __forceinline__ void ground_body(const wbc::ModelC* __restrict__ mp, const GroundArgs& a) {
+// TERRAIN: `lds` is the block's TERRAIN_LDS_DOUBLES of LDS; the table is staged into it once, before anything else, and every foot
+// of every substep reads its profile from there (a lane carries the address of its profile and its scale through the loop, no
+// knot).  Without TERRAIN, ta and lds are not touched.
+template <bool STEP, bool TERRAIN>
+__device__ __forceinline__ void ground_body(const wbc::ModelC* __restrict__ mp, const GroundArgs& a, const TerrainArgs& ta, double* lds) {
   using namespace wbc;
+  if (TERRAIN) {
+    const int words = ta.count * TERRAIN_STRIDE;   // count <= TERRAIN_MAX_PROFILES: checked by wbc_ground_set_terrain
+    for (int k = threadIdx.x; k < words; k += GROUND_BLOCK) lds[k] = ta.table[k];
+    __syncthreads();
+  }
   const int t = blockIdx.x * GROUND_BLOCK + threadIdx.x;
   const int l = t & 3;
   const int r = t >> 2;
@@ -140,6 +158,15 @@ __device__ __forceinline__ void ground_body(const wbc::ModelC* __restrict__ mp, 
     clip |= fabs(tq[k]) > a.tau_max * (1.0 + PLANT_CLIP_TOL);
   }
   nf |= !(mu > 0.0) | not_finite(mu) | !(s_p > 0.0) | not_finite(s_p);
+  const double* tab = nullptr;
+  double tscale = 1.0;
+  if (TERRAIN) {
+    const int id = ta.id ? (int)ta.id[i] : 0;
+    tscale = ta.scale ? ta.scale[i] : 1.0;
+    const bool tbad = (id >= ta.count) | not_finite(tscale);
+    nf |= tbad;
+    tab = lds + (tbad ? 0 : id) * TERRAIN_STRIDE;   // a bad instance computes on profile 0 and stores nothing of it
+  }
   double tau_a[3];
 #pragma unroll
   for (int k = 0; k < 3; k++) tau_a[k] = fmin(fmax(tq[k], -a.tau_max), a.tau_max);
@@ -152,7 +179,7 @@ __device__ __forceinline__ void ground_body(const wbc::ModelC* __restrict__ mp, 
     const double h = a.h;
 #pragma unroll 1
     for (int s = 0; s < a.substeps; s++) {
-      fb = ground_eval(m, l, law, mu, s_p, we, qb, vb, th, qd, tau_a, vdb, vdl, f);
+      fb = ground_eval<TERRAIN>(m, l, law, mu, s_p, we, qb, vb, th, qd, tau_a, vdb, vdl, f, tab, tscale);
       slip |= fb;
 #pragma unroll
       for (int k = 0; k < 6; k++) nf |= not_finite(vdb[k]);
@@ -168,7 +195,7 @@ __device__ __forceinline__ void ground_body(const wbc::ModelC* __restrict__ mp, 
 #pragma unroll
     for (int k = 0; k < 7; k++) nf |= not_finite(qb[k]);
   } else {
-    fb = ground_eval(m, l, law, mu, s_p, we, qb, vb, th, qd, tau_a, vdb, vdl, f);
+    fb = ground_eval<TERRAIN>(m, l, law, mu, s_p, we, qb, vb, th, qd, tau_a, vdb, vdl, f, tab, tscale);
     slip = fb;
 #pragma unroll
     for (int k = 0; k < 6; k++) nf |= not_finite(vdb[k]);
@@ -180,7 +207,7 @@ __device__ __forceinline__ void ground_body(const wbc::ModelC* __restrict__ mp, 
   const int all = qor(mine);
   const bool bad = all & 1;
   int bits = (bad ? GROUND_BAD : 0) | ((all & 2) ? GROUND_CLIP : 0);
-  if (!bad) bits |= ((all & 4) ? GROUND_SLIP : 0) | (!(qb[6] > a.fall_height) ? GROUND_FELL : 0);
+  if (!bad) bits |= ((all & 4) ? GROUND_SLIP : 0) | (ground_fell<TERRAIN>(qb, a.fall_height, tab, tscale) ? GROUND_FELL : 0);
   // ---------------- stores.  The store addresses are formed afresh from an index the compiler cannot tie to the loads': otherwise
   // it keeps the ~20 row addresses of the loads alive over the substep loop, and they spill.
   if (!live) return;
@@ -220,16 +247,26 @@ __device__ __forceinline__ void ground_body(const wbc::ModelC* __restrict__ mp, 
 
 // stable kernel names (rocprofv3 --kernel-trace)
 __global__ void __launch_bounds__(GROUND_BLOCK) wbc_ground_step_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a) {
-  ground_body<true>(m, a);
+  ground_body<true, false>(m, a, TerrainArgs{}, nullptr);
 }
 __global__ void __launch_bounds__(GROUND_BLOCK) wbc_ground_forward_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a) {
-  ground_body<false>(m, a);
+  ground_body<false, false>(m, a, TerrainArgs{}, nullptr);
+}
+__global__ void __launch_bounds__(GROUND_BLOCK) wbc_ground_terrain_step_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a, TerrainArgs ta) {
+  __shared__ double lds[TERRAIN_LDS_DOUBLES];
+  ground_body<true, true>(m, a, ta, lds);
+}
+__global__ void __launch_bounds__(GROUND_BLOCK) wbc_ground_terrain_forward_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a, TerrainArgs ta) {
+  __shared__ double lds[TERRAIN_LDS_DOUBLES];
+  ground_body<false, true>(m, a, ta, lds);
 }
 
 struct wbc_ground_s {
   int device;
   wbc_ground_params params;
   wbc::ModelC* d_model;
+  double* d_terrain;           // the packed table, TERRAIN_LDS_DOUBLES doubles, allocated by the first wbc_ground_set_terrain
+  TerrainArgs terrain;         // count == 0: no terrain
 };
 
 namespace {
@@ -255,7 +292,12 @@ int substeps_for(const char* fn, wbc_ground g, double dt) {
 
 int launch_ground(wbc_ground g, hipStream_t s, bool step, const GroundArgs& a) {
   const dim3 grid((unsigned)(((size_t)a.n * 4 + GROUND_BLOCK - 1) / GROUND_BLOCK));
-  if (step)
+  if (g->terrain.count > 0) {
+    if (step)
+      hipLaunchKernelGGL(wbc_ground_terrain_step_kernel, grid, dim3(GROUND_BLOCK), 0, s, g->d_model, a, g->terrain);
+    else
+      hipLaunchKernelGGL(wbc_ground_terrain_forward_kernel, grid, dim3(GROUND_BLOCK), 0, s, g->d_model, a, g->terrain);
+  } else if (step)
     hipLaunchKernelGGL(wbc_ground_step_kernel, grid, dim3(GROUND_BLOCK), 0, s, g->d_model, a);
   else
     hipLaunchKernelGGL(wbc_ground_forward_kernel, grid, dim3(GROUND_BLOCK), 0, s, g->d_model, a);
@@ -340,6 +382,8 @@ int wbc_ground_create(const wbc_model* model, const wbc_ground_params* params, i
   g->device = device;
   g->params = P;
   g->d_model = d;
+  g->d_terrain = nullptr;
+  g->terrain = TerrainArgs{};
   *out = g;
   return 0;
 }
@@ -349,6 +393,7 @@ int wbc_ground_destroy(wbc_ground g) {
   wbc::DeviceGuard device_guard_(g->device);
   (void)hipDeviceSynchronize();   // a launch still reading the model
   if (g->d_model) (void)hipFree(g->d_model);
+  if (g->d_terrain) (void)hipFree(g->d_terrain);
   delete g;
   return 0;
 }
@@ -414,6 +459,57 @@ int wbc_ground_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int*
   WBC_ON_DEVICE(g->device, gfail);
   hipFuncAttributes fa;
   GROUND_TRY(hipFuncGetAttributes(&fa, (const void*)wbc_ground_step_kernel));
+  if (num_vgpr) *num_vgpr = fa.numRegs;
+  if (scratch_bytes) *scratch_bytes = (int)fa.localSizeBytes;
+  if (lds_bytes) *lds_bytes = (int)fa.sharedSizeBytes;
+  if (block_threads) *block_threads = GROUND_BLOCK;
+  return 0;
+}
+
+int wbc_terrain_check(const wbc_terrain_profile* profiles, int count) {
+  char b[256];
+  if (!profiles) return gmisuse("wbc_terrain_check: null profiles");
+  if (count < 1 || count > WBC_GROUND_MAX_PROFILES) return gmisuse("wbc_terrain_check: count must be 1 .. WBC_GROUND_MAX_PROFILES (16)");
+  for (int p = 0; p < count; p++) {
+    const wbc_terrain_profile& t = profiles[p];
+    const char* what = wbc::terrain_profile_error(t.nk, t.x0, t.y0, t.yaw, t.s, t.h);
+    if (what) { snprintf(b, sizeof b, "wbc_terrain_check: profile %d: %s", p, what); return gmisuse(b); }
+  }
+  return 0;
+}
+
+int wbc_ground_set_terrain(wbc_ground g, const wbc_terrain_profile* profiles, int count, const uint8_t* terrain_id,
+                           const double* terrain_scale) {
+  if (!g) return gmisuse("wbc_ground_set_terrain: null ground handle");
+  if (!profiles || count == 0) {
+    g->terrain = TerrainArgs{};
+    return 0;
+  }
+  const int rc = wbc_terrain_check(profiles, count);
+  if (rc) return rc;
+  static_assert(WBC_GROUND_MAX_PROFILES == wbc::TERRAIN_MAX_PROFILES, "the header's limit is the table's");
+  double table[TERRAIN_LDS_DOUBLES];
+  for (int p = 0; p < count; p++) {
+    const wbc_terrain_profile& t = profiles[p];
+    wbc::terrain_pack(t.nk, t.x0, t.y0, t.yaw, t.s, t.h, table + p * wbc::TERRAIN_STRIDE);
+  }
+  WBC_ON_DEVICE(g->device, gfail);
+  if (!g->d_terrain) GROUND_TRY(hipMalloc(&g->d_terrain, sizeof table));
+  GROUND_TRY(hipDeviceSynchronize());   // a launch still reading the previous table
+  g->terrain = TerrainArgs{};
+  GROUND_TRY(hipMemcpy(g->d_terrain, table, (size_t)count * wbc::TERRAIN_STRIDE * sizeof(double), hipMemcpyHostToDevice));
+  g->terrain.table = g->d_terrain;
+  g->terrain.id = terrain_id;
+  g->terrain.scale = terrain_scale;
+  g->terrain.count = count;
+  return 0;
+}
+
+int wbc_ground_terrain_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
+  if (!g) return gmisuse("wbc_ground_terrain_kernel_info: null ground handle");
+  WBC_ON_DEVICE(g->device, gfail);
+  hipFuncAttributes fa;
+  GROUND_TRY(hipFuncGetAttributes(&fa, (const void*)wbc_ground_terrain_step_kernel));
   if (num_vgpr) *num_vgpr = fa.numRegs;
   if (scratch_bytes) *scratch_bytes = (int)fa.localSizeBytes;
   if (lds_bytes) *lds_bytes = (int)fa.sharedSizeBytes;

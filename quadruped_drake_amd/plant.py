@@ -8,7 +8,8 @@ lookup -> controller tick -> plant step on the device.  Torch tensors and torch'
 
 `GroundContactPlant` (include/wbc_ground.h) has a ground instead of held feet: a compliant half-space z = 0 whose force on each
 foot is an explicit function of the state, so feet lift off, land and slip and a robot that tips falls.  One `step` runs all
-explicit substeps of a control period in a single launch.  `closed_loop` takes either plant.
+explicit substeps of a control period in a single launch.  `set_terrain` replaces the plane by per-instance slopes, ramps and
+steps (terrain.py).  `closed_loop` takes either plant.
 """
 import ctypes as C
 import math
@@ -55,6 +56,10 @@ def _L():
         l.wbc_ground_step.argtypes = [P, P, C.c_int, C.c_int, C.c_double] + [P] * 11
         l.wbc_ground_rollout.argtypes = [P, P, P, P, C.c_int, C.c_double, C.c_int, C.c_int] + [P] * 17
         l.wbc_ground_kernel_info.argtypes = [P] + [C.POINTER(C.c_int)] * 4
+        if hasattr(l, "wbc_terrain_check"):   # absent from an older kernel build under A/B timing (WBC_HIP_LIB)
+            l.wbc_terrain_check.argtypes = [P, C.c_int]
+            l.wbc_ground_set_terrain.argtypes = [P, P, C.c_int, P, P]
+            l.wbc_ground_terrain_kernel_info.argtypes = [P] + [C.POINTER(C.c_int)] * 4
         _bound = l
     return _bound
 
@@ -195,11 +200,43 @@ class GroundContactPlant:
         _lib.check(L.wbc_ground_create(C.byref(m), C.byref(p), self.device, C.byref(h)))
         self._h = h
         self._L = L
+        self._terrain = None
 
     def close(self):
         if getattr(self, "_h", None):
             self._L.wbc_ground_destroy(self._h)
             self._h = None
+            self._terrain = None
+
+    def set_terrain(self, profiles, terrain_id=None, terrain_scale=None):
+        """Put the ground of terrain.py under the feet: `profiles`, a list of 1 .. 16 terrain.Profile, or None for the plane z = 0
+        again.  Instance i stands on profiles[terrain_id[i]] (uint8 [N] on the plant's device; None: profile 0) scaled in height
+        by terrain_scale[i] (float64 [N]; None: 1.0).  Both tensors must cover the N of every later forward / step / closed_loop
+        and are kept alive here.  An id beyond the list or a non-finite scale makes the instance BAD.  Synchronises the device."""
+        import torch
+        if profiles is None:
+            if terrain_id is not None or terrain_scale is not None:
+                raise ValueError("set_terrain: terrain_id / terrain_scale need profiles")
+            _lib.check(self._L.wbc_ground_set_terrain(self._h, None, 0, None, None))
+            self._terrain = None
+            return
+        from . import terrain as _terrain
+        profiles = list(profiles)
+        if not profiles or not all(isinstance(p, _terrain.Profile) for p in profiles):
+            raise ValueError("set_terrain: profiles must be a non-empty list of terrain.Profile")
+        n = None
+        for a in (terrain_id, terrain_scale):
+            if a is not None and isinstance(a, torch.Tensor) and a.dim() == 1:
+                n = int(a.shape[0]) if n is None else n
+        pid = _dev_ptr(terrain_id, 0, n, torch.uint8, "terrain_id", self.device, True)
+        psc = _dev_ptr(terrain_scale, 0, n, torch.float64, "terrain_scale", self.device, True)
+        arr = _terrain.c_array(profiles)
+        _lib.check(self._L.wbc_ground_set_terrain(self._h, C.cast(arr, C.c_void_p), len(profiles), pid, psc))
+        self._terrain = (profiles, terrain_id, terrain_scale, n)
+
+    def _check_terrain_n(self, n):
+        if self._terrain is not None and self._terrain[3] is not None and self._terrain[3] < n:
+            raise ValueError("terrain_id / terrain_scale hold %d instances, the call has %d" % (self._terrain[3], n))
 
     def __del__(self):
         try:
@@ -219,6 +256,7 @@ class GroundContactPlant:
         import torch
         n = int(q.shape[1])
         d = self.device
+        self._check_terrain_n(n)
         return n, [_dev_ptr(q, 19, n, torch.float64, "q", d), _dev_ptr(v, 18, n, torch.float64, "v", d),
                    _dev_ptr(tau, 12, n, torch.float64, "tau", d), _dev_ptr(mu, 0, n, torch.float64, "mu", d, True),
                    _dev_ptr(mass_scale, 0, n, torch.float64, "mass_scale", d, True),
@@ -261,6 +299,12 @@ class GroundContactPlant:
         _lib.check(self._L.wbc_ground_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
 
+    def terrain_kernel_info(self):
+        """kernel_info() of the step kernel that runs while a terrain is set."""
+        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self._L.wbc_ground_terrain_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
+
 
 def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=None, plant_mu=None, plant_mass_scale=None, counts=None,
                 ext_wrench=None):
@@ -279,6 +323,8 @@ def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=No
         raise ValueError("closed_loop: ext_wrench needs a GroundContactPlant")
     n = int(q.shape[1])
     d = plant.device
+    if ground:
+        plant._check_terrain_n(n)
     ptr = lambda a, rows, dt_, name, opt=False: _dev_ptr(a, rows, n, dt_, name, d, opt)
     pq, pv, pt = ptr(q, 19, torch.float64, "q"), ptr(v, 18, torch.float64, "v"), ptr(time, 0, torch.float64, "time")
     pmu, pms = ptr(mu, 0, torch.float64, "mu", True), ptr(mass_scale, 0, torch.float64, "mass_scale", True)

@@ -9,7 +9,12 @@ What replaces what: the initial state is simulate.py:171-179; `--planner basic` 
 (planners/towr.py; TOWR itself is out of scope); the controller is the fused tick; Drake's MultibodyPlant(time_step=dt)
 and contact solver (simulate.py:38-64) are replaced by the rigid-contact forward step of `wbc_rollout` (DESIGN.md
 section 9: stance feet are held by the QP's contact rows, nothing slips or lifts on its own) -- a harness for the
-controllers, not a physics engine.  No visualiser, no LCM."""
+controllers, not a physics engine.  No visualiser, no LCM.
+
+`--plant` chooses what the torques act on: `plan` (the default, the above), `rigid` (plant.RigidContactPlant: stance feet held,
+PULL / CONE reported) or `ground` (plant.GroundContactPlant: a compliant ground on which feet lift, land and slip and a robot
+can fall).  `--terrain NAME[:PARAM]` (with `--plant ground` only; terrain.SPECS) puts a slope, a ramp step, stairs or a ridge
+under the feet; the controllers still assume a level ground."""
 import argparse
 import json
 import sys
@@ -32,6 +37,9 @@ def parse(argv=None):
     ap.add_argument("--model", default="mini_cheetah")
     ap.add_argument("--log-every", type=int, default=10, help="ticks between two samples of the metrics log")
     ap.add_argument("--log", default=None, help="write the log (t, V, err, res, Vdot of every instance) to this .npz")
+    ap.add_argument("--plant", default="plan", choices=("plan", "rigid", "ground"),
+                    help="what the torques act on: the controller's own plan, the rigid-contact plant or the compliant-ground plant")
+    ap.add_argument("--terrain", default=None, help="--plant ground only: NAME[:PARAM], e.g. slope:0.2 (flat, slope, ramp_step, stairs, ridge)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
@@ -39,6 +47,14 @@ def parse(argv=None):
         a.dt = 5e-3 if a.control in ("ID", "CLF") else 1e-3
     if a.planner == "towr" and not a.messages:
         ap.error("--planner towr needs --messages FILE (a recorded trunk_state stream)")
+    if a.terrain is not None:
+        if a.plant != "ground":
+            ap.error("--terrain needs --plant ground")
+        from . import terrain
+        try:
+            terrain.from_spec(a.terrain)
+        except ValueError as e:
+            ap.error(str(e))
     if a.n < 1 or a.sim_time <= 0 or a.dt <= 0 or a.log_every < 1:
         ap.error("--n, --sim-time, --dt and --log-every must be positive")
     return a
@@ -63,6 +79,20 @@ def run(a):
     if a.perturb > 0 and a.n > 1:
         q0[7:, 1:] += np.random.default_rng(a.seed).uniform(-a.perturb, a.perturb, (12, a.n - 1))
     ctrl = cls(model=a.model, max_batch=a.n, device=a.device)
+    plant = counts = None
+    if a.plant != "plan":
+        from . import plant as plant_mod
+        if a.plant == "rigid":
+            plant = plant_mod.RigidContactPlant(a.model, device=a.device)
+        else:
+            plant = plant_mod.GroundContactPlant(a.model, device=a.device)
+            if a.terrain is not None:
+                from . import terrain
+                prof = terrain.from_spec(a.terrain)
+                plant.set_terrain([prof])
+                quat, pos = terrain.stance_pose(prof, 0.0, 0.0, float(q0[6, 0]))     # square on the ground under the start
+                q0[0:4] = quat[:, None]; q0[4:7] = pos[:, None]
+        counts = torch.zeros((4, a.n), dtype=torch.int32, device=dev)
     q, v = torch.tensor(q0, device=dev), torch.tensor(v0, device=dev)
     time = torch.zeros(a.n, dtype=torch.float64, device=dev)
     steps = int(round(a.sim_time / a.dt))
@@ -72,7 +102,10 @@ def run(a):
     done = 0
     while done < steps:
         k = min(a.log_every, steps - done)
-        tau, met, st, tg, mk = ctrl.rollout(traj, k, a.dt, q, v, time)
+        if plant is None:
+            tau, met, st, tg, mk = ctrl.rollout(traj, k, a.dt, q, v, time)
+        else:
+            met = plant_mod.closed_loop(ctrl, plant, traj, k, a.dt, q, v, time, counts=counts)[1]
         done += k
         ts.append(done * a.dt); mets.append(met.clone())
     ctrl.sync(); wall = _time.perf_counter() - t0
@@ -80,6 +113,11 @@ def run(a):
     out = dict(t=np.array(ts), metrics=torch.stack(mets).cpu().numpy(), status_nonzero=int(s["status_nonzero"]),
                ticks=int(s["ticks"]), q=q.cpu().numpy(), v=v.cpu().numpy(), ticks_per_second=s["ticks"] / wall,
                iters_mean=s["iters_sum"] / max(s["ticks"], 1.0))
+    if plant is not None:
+        c = counts.cpu().numpy()
+        names = ("slip", "fell", "clip", "bad") if a.plant == "ground" else ("pull", "cone", "clip", "bad")
+        out["plant_flags"] = {nm: int((c[b] > 0).sum()) for b, nm in enumerate(names)}      # instances that ever raised the flag
+        plant.close()
     ctrl.close(); traj.close()
     return out
 
@@ -91,11 +129,16 @@ def main(argv=None):
         np.savez_compressed(a.log, t=r["t"], V=r["metrics"][:, 0], err=r["metrics"][:, 1], res=r["metrics"][:, 2],
                             Vdot=r["metrics"][:, 3], q=r["q"], v=r["v"])
     m = r["metrics"]
+    extra = {}
+    if a.plant != "plan":
+        extra = {"plant": a.plant, "terrain": a.terrain, "plant_flags": r["plant_flags"]}
+        if a.plant == "ground":
+            extra.update(FELL=r["plant_flags"]["fell"], SLIP=r["plant_flags"]["slip"])
     print(json.dumps({"control": a.control, "planner": a.planner, "scenario": a.scenario if a.planner == "basic" else a.messages,
                       "n": a.n, "sim_time": a.sim_time, "dt": a.dt, "ticks": r["ticks"], "status_nonzero": r["status_nonzero"],
                       "ticks_per_second": r["ticks_per_second"], "active_set_iterations_mean": r["iters_mean"],
                       "final": {"V": float(m[-1, 0].mean()), "err": float(m[-1, 1].mean()), "Vdot": float(m[-1, 3].mean())},
-                      "body_height_final": [float(r["q"][6].min()), float(r["q"][6].max())]}))
+                      "body_height_final": [float(r["q"][6].min()), float(r["q"][6].max())], **extra}))
     return 0 if r["status_nonzero"] == 0 else 1
 
 

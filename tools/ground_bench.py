@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measurements of the compliant-ground plant (include/wbc_ground.h) for profiles/r08/ground.md.
 
-    python tools/ground_bench.py [--launches 100] [--loop-steps 300] [--json out.json]
+    python tools/ground_bench.py [--launches 100] [--loop-steps 300] [--json out.json] [--terrain NAME[:PARAM]]
 
   * wbc_ground_step device time at N = 4096 and 32768 (Mini Cheetah standing on the ground, zero torque) with S = 8 and S = 16
     substeps of a 1 ms period: HIP events around back-to-back launches after a warm-up.  Per step, and per substep as
@@ -9,6 +9,8 @@
   * the yardstick, timed in the same run: the rigid plant's wbc_plant_step (tools/plant_bench.py's time_plant_step);
   * time per 1 ms closed-loop tick at N = 4096, MPTC on plant_bench's trot trajectory: wbc_ground_rollout (default 16 substeps)
     against wbc_plant_rollout (the three-launch loop with the rigid plant) and the persistent wbc_rollout.
+With --terrain (terrain.SPECS, e.g. slope:0.1) only the N = 4096 step is timed, flat and on the terrain back to back, with
+the per-substep ratio of the two and the resources of both step kernels.
 For the rocprofv3 figure run the same script under `rocprofv3 --kernel-trace --stats -- python tools/ground_bench.py`."""
 import argparse
 import json
@@ -21,18 +23,27 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def time_ground_step(n, substeps, launches, warm=10, dt=1e-3, model="mini_cheetah"):
+def time_ground_step(n, substeps, launches, warm=10, dt=1e-3, model="mini_cheetah", terrain=None):
     import numpy as np
     import torch
     import ground_oracle as go
     from quadruped_drake_amd import GroundContactPlant
     _, q0, v0 = go.drop_state(model, height=0.0, n=n)
+    if terrain is not None:      # square on the terrain, spread along it, every second robot on a ground scaled by 0.5
+        from quadruped_drake_amd import terrain as tr
+        prof = tr.from_spec(terrain)
+        scale = np.where(np.arange(n) % 2 == 0, 1.0, 0.5)
+        for i, x in enumerate(np.linspace(-1.0, 1.0, n)):
+            quat, pos = tr.stance_pose(prof, x, 0.0, q0[6, i], scale[i])
+            q0[0:4, i], q0[4:7, i] = quat, pos
     q0[7:] += np.random.default_rng(1).uniform(-0.02, 0.02, (12, n))
     dev = "cuda:0"
     q, v = torch.tensor(q0, device=dev), torch.tensor(v0, device=dev)
     tau = torch.zeros((12, n), dtype=torch.float64, device=dev)
     plant = GroundContactPlant(model, device=0, max_substep=dt / substeps)
     assert plant.substeps(dt) == substeps
+    if terrain is not None:
+        plant.set_terrain([tr.flat(0.0), prof], torch.ones(n, dtype=torch.uint8, device=dev), torch.tensor(scale, device=dev))
     out = plant.step(q, v, tau, dt)
     for _ in range(warm):
         plant.step(q, v, tau, dt, out=out)
@@ -45,9 +56,9 @@ def time_ground_step(n, substeps, launches, warm=10, dt=1e-3, model="mini_cheeta
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3 / launches
     flags = out[2].cpu().numpy()
-    info = plant.kernel_info()
+    info = plant.kernel_info() if terrain is None else plant.terrain_kernel_info()
     plant.close()
-    return {"n": n, "substeps": substeps, "us_per_step": us, "launches": launches, "bad": int(((flags & 8) != 0).sum()),
+    return {"n": n, "substeps": substeps, "terrain": terrain, "us_per_step": us, "launches": launches, "bad": int(((flags & 8) != 0).sum()),
             "fell": int(((flags & 2) != 0).sum()), "kernel": info}
 
 
@@ -95,8 +106,25 @@ def main():
     ap.add_argument("--launches", type=int, default=100)
     ap.add_argument("--loop-steps", type=int, default=300)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--terrain", default=None, help="NAME[:PARAM] of quadruped_drake_amd.terrain.SPECS: time the N = 4096 step flat and on it")
     a = ap.parse_args()
     out = {}
+    if a.terrain:
+        per = {}
+        for rep_ in range(2):                    # flat, terrain, flat, terrain: the second pair is the figure, the first shows the drift
+            for name, ter in (("flat", None), ("terrain", a.terrain)):
+                s = {sub: time_ground_step(4096, sub, a.launches, terrain=ter) for sub in (8, 16)}
+                per[name] = (s[16]["us_per_step"] - s[8]["us_per_step"]) / 8.0
+                for sub in (8, 16):
+                    out["%s_step_4096_S%d_run%d" % (name, sub, rep_)] = s[sub]
+                    print(json.dumps(s[sub]), flush=True)
+            out["substep_4096_run%d" % rep_] = {"flat_us": per["flat"], "terrain_us": per["terrain"], "ratio": per["terrain"] / per["flat"]}
+            print(json.dumps(out["substep_4096_run%d" % rep_]), flush=True)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     for n in (4096, 32768):
         r = plant_bench.time_plant_step(n, 4 * a.launches)
         out["plant_step_%d" % n] = r
