@@ -17,26 +17,10 @@
 #include "wbc_model.hpp"
 #include "wbc_tick.hpp"
 #include "wbc_ground.hpp"
-#include "wbc_device_guard.hpp"
-
-extern "C" void wbc_set_error_(const char* msg);   // wbc_kernels.hip: the buffer wbc_last_error() returns
+#include "wbc_quad.hpp"
+#include "wbc_plant_host.hpp"
 
 namespace {
-
-int gfail(const char* what, hipError_t e) {
-  char b[512];
-  snprintf(b, sizeof b, "%s: %s", what, hipGetErrorString(e));
-  wbc_set_error_(b);
-  return -2;
-}
-int gmisuse(const char* what) { wbc_set_error_(what); return -1; }
-#define GROUND_TRY(x)                               \
-  do {                                              \
-    hipError_t e_ = (x);                            \
-    if (e_ != hipSuccess) return gfail(#x, e_);     \
-  } while (0)
-
-constexpr int GROUND_BLOCK = 64;   // one wavefront per workgroup: 16 robots
 
 struct GroundArgs {
   int n, ld, substeps;
@@ -64,24 +48,6 @@ struct TerrainArgs {
   int count;
 };
 constexpr int TERRAIN_LDS_DOUBLES = wbc::TERRAIN_MAX_PROFILES * wbc::TERRAIN_STRIDE;   // 5 KB
-
-// quad_perm DPP move of a double: CTRL = p0 | p1 << 2 | p2 << 4 | p3 << 6 (lane j of the quad reads lane p_j)
-template <int CTRL> __device__ __forceinline__ double qmove(double x) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-template <int CTRL> __device__ __forceinline__ int qmove_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, false); }
-constexpr int QP_XOR1 = 0xB1, QP_XOR2 = 0x4E;                 // [1 0 3 2], [2 3 0 1]
-// sum over the quad, the same bits on every lane: (x0 + x1) + (x2 + x3)
-__device__ __forceinline__ double qsum(double x) {
-  const double a = x + qmove<QP_XOR1>(x);
-  return a + qmove<QP_XOR2>(a);
-}
-__device__ __forceinline__ int qor(int x) {
-  const int a = x | qmove_i<QP_XOR1>(x);
-  return a | qmove_i<QP_XOR2>(a);
-}
 
 // One force evaluation at the state in registers: base accelerations (replicated), the own leg's joint accelerations and foot
 // force.  Returns ground_foot_force's bits of the own foot.
@@ -114,10 +80,10 @@ __device__ __forceinline__ void ground_body(const wbc::ModelC* __restrict__ mp, 
   using namespace wbc;
   if (TERRAIN) {
     const int words = ta.count * TERRAIN_STRIDE;   // count <= TERRAIN_MAX_PROFILES: checked by wbc_ground_set_terrain
-    for (int k = threadIdx.x; k < words; k += GROUND_BLOCK) lds[k] = ta.table[k];
+    for (int k = threadIdx.x; k < words; k += QUAD_BLOCK) lds[k] = ta.table[k];
     __syncthreads();
   }
-  const int t = blockIdx.x * GROUND_BLOCK + threadIdx.x;
+  const int t = blockIdx.x * QUAD_BLOCK + threadIdx.x;
   const int l = t & 3;
   const int r = t >> 2;
   const bool live = r < a.n;
@@ -246,17 +212,17 @@ __device__ __forceinline__ void ground_body(const wbc::ModelC* __restrict__ mp, 
 }  // namespace
 
 // stable kernel names (rocprofv3 --kernel-trace)
-__global__ void __launch_bounds__(GROUND_BLOCK) wbc_ground_step_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a) {
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_ground_step_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a) {
   ground_body<true, false>(m, a, TerrainArgs{}, nullptr);
 }
-__global__ void __launch_bounds__(GROUND_BLOCK) wbc_ground_forward_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a) {
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_ground_forward_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a) {
   ground_body<false, false>(m, a, TerrainArgs{}, nullptr);
 }
-__global__ void __launch_bounds__(GROUND_BLOCK) wbc_ground_terrain_step_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a, TerrainArgs ta) {
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_ground_terrain_step_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a, TerrainArgs ta) {
   __shared__ double lds[TERRAIN_LDS_DOUBLES];
   ground_body<true, true>(m, a, ta, lds);
 }
-__global__ void __launch_bounds__(GROUND_BLOCK) wbc_ground_terrain_forward_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a, TerrainArgs ta) {
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_ground_terrain_forward_kernel(const wbc::ModelC* __restrict__ m, GroundArgs a, TerrainArgs ta) {
   __shared__ double lds[TERRAIN_LDS_DOUBLES];
   ground_body<false, true>(m, a, ta, lds);
 }
@@ -272,36 +238,29 @@ struct wbc_ground_s {
 namespace {
 
 int check_ground_args(const char* fn, wbc_ground g, int n, int ld, const void* q, const void* v, const void* tau) {
-  char b[256];
-  if (n < 0 || n > WBC_MAX_LD) { snprintf(b, sizeof b, "%s: n out of range (0 .. WBC_MAX_LD)", fn); return gmisuse(b); }
-  if (ld > WBC_MAX_LD) { snprintf(b, sizeof b, "%s: ld exceeds WBC_MAX_LD", fn); return gmisuse(b); }
-  if (n > 0 && ld < n) { snprintf(b, sizeof b, "%s: ld must be >= n", fn); return gmisuse(b); }
-  if (!g) { snprintf(b, sizeof b, "%s: null ground handle", fn); return gmisuse(b); }
-  if (n > 0 && (!q || !v || !tau)) { snprintf(b, sizeof b, "%s: q, v and tau are required", fn); return gmisuse(b); }
-  return 0;
+  return wbc::plant_check_batch(fn, g, "ground", n, ld, q && v && tau, "q, v and tau");
 }
 
 // the substeps of a period dt; < 0 with the message set when dt is not a positive finite time or needs more than 2^20 substeps
 int substeps_for(const char* fn, wbc_ground g, double dt) {
-  char b[256];
-  if (!(dt > 0.0) || dt == INFINITY) { snprintf(b, sizeof b, "%s: dt must be positive and finite", fn); return gmisuse(b); }
+  if (!(dt > 0.0) || dt == INFINITY) return wbc::plant_misuse(fn, "dt must be positive and finite");
   const int s = wbc::ground_substeps(dt, g->params.max_substep);
-  if (s <= 0) { snprintf(b, sizeof b, "%s: dt / max_substep exceeds 2^20 substeps", fn); return gmisuse(b); }
+  if (s <= 0) return wbc::plant_misuse(fn, "dt / max_substep exceeds 2^20 substeps");
   return s;
 }
 
 int launch_ground(wbc_ground g, hipStream_t s, bool step, const GroundArgs& a) {
-  const dim3 grid((unsigned)(((size_t)a.n * 4 + GROUND_BLOCK - 1) / GROUND_BLOCK));
+  const dim3 grid = wbc::plant_grid(a.n), block(wbc::QUAD_BLOCK);
   if (g->terrain.count > 0) {
     if (step)
-      hipLaunchKernelGGL(wbc_ground_terrain_step_kernel, grid, dim3(GROUND_BLOCK), 0, s, g->d_model, a, g->terrain);
+      hipLaunchKernelGGL(wbc_ground_terrain_step_kernel, grid, block, 0, s, g->d_model, a, g->terrain);
     else
-      hipLaunchKernelGGL(wbc_ground_terrain_forward_kernel, grid, dim3(GROUND_BLOCK), 0, s, g->d_model, a, g->terrain);
+      hipLaunchKernelGGL(wbc_ground_terrain_forward_kernel, grid, block, 0, s, g->d_model, a, g->terrain);
   } else if (step)
-    hipLaunchKernelGGL(wbc_ground_step_kernel, grid, dim3(GROUND_BLOCK), 0, s, g->d_model, a);
+    hipLaunchKernelGGL(wbc_ground_step_kernel, grid, block, 0, s, g->d_model, a);
   else
-    hipLaunchKernelGGL(wbc_ground_forward_kernel, grid, dim3(GROUND_BLOCK), 0, s, g->d_model, a);
-  GROUND_TRY(hipGetLastError());
+    hipLaunchKernelGGL(wbc_ground_forward_kernel, grid, block, 0, s, g->d_model, a);
+  WBC_PLANT_TRY(hipGetLastError());
   return 0;
 }
 
@@ -318,26 +277,7 @@ GroundArgs make_args(wbc_ground g, int n, int ld, int substeps, double dt, doubl
   return a;
 }
 
-int model_of(const char* fn, const wbc_model* model, wbc::ModelC* m) {
-  char b[384];
-  if (wbc::model_from_flat(model->flat, m)) { snprintf(b, sizeof b, "%s: joint axes must be axis-aligned", fn); return gmisuse(b); }
-  if (!wbc::model_axes_are_xyy(m)) {
-    snprintf(b, sizeof b, "%s: unsupported kinematic tree -- legs with the abduction joint about +-x and the hip and knee joints "
-                          "about +-y (Mini Cheetah, ANYmal)", fn);
-    return gmisuse(b);
-  }
-  return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int wbc_ground_params_default(const wbc_model* model, wbc_ground_params* out) {
-  if (!model || !out) return gmisuse("wbc_ground_params_default: null argument");
-  wbc::ModelC m;
-  const int rc = model_of("wbc_ground_params_default", model, &m);
-  if (rc) return rc;
+void default_params(const wbc::ModelC& m, wbc_ground_params* out) {
   wbc::ground_default_law(m, &out->stiffness, &out->dissipation);
   out->mu = 1.0;
   out->v_stiction = wbc::GROUND_V_STICTION;
@@ -345,39 +285,37 @@ int wbc_ground_params_default(const wbc_model* model, wbc_ground_params* out) {
   out->tau_max = INFINITY;
   out->max_substep = wbc::GROUND_MAX_SUBSTEP;
   out->fall_height = 0.0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wbc_ground_params_default(const wbc_model* model, wbc_ground_params* out) {
+  if (!model || !out) return wbc::plant_misuse("wbc_ground_params_default: null argument");
+  wbc::ModelC m;
+  const int rc = wbc::plant_model_axes("wbc_ground_params_default", model, &m);
+  if (rc) return rc;
+  default_params(m, out);
   return 0;
 }
 
 int wbc_ground_create(const wbc_model* model, const wbc_ground_params* params, int device, wbc_ground* out) {
-  if (!model || !out) return gmisuse("wbc_ground_create: null argument");
+  if (!model || !out) return wbc::plant_misuse("wbc_ground_create: null argument");
   wbc::ModelC m;
-  int rc = model_of("wbc_ground_create", model, &m);
+  int rc = wbc::plant_model("wbc_ground_create", model, &m);
   if (rc) return rc;
-  bool seen_q[12] = {0}, seen_a[12] = {0};
-  int qp[12], ap[12];
-  for (int i = 0; i < 12; i++) {
-    qp[i] = model->q_perm[i]; ap[i] = model->act_perm[i];
-    if (qp[i] < 0 || qp[i] >= 12 || ap[i] < 0 || ap[i] >= 12 || seen_q[qp[i]] || seen_a[ap[i]])
-      return gmisuse("wbc_ground_create: q_perm/act_perm must be permutations of 0..11");
-    seen_q[qp[i]] = seen_a[ap[i]] = true;
-  }
-  wbc::model_set_perms(&m, qp, ap);
   wbc_ground_params P;
-  wbc_ground_params_default(model, &P);
+  default_params(m, &P);
   if (params) P = *params;
   const bool fin = P.stiffness < INFINITY && P.dissipation < INFINITY && P.mu < INFINITY && P.v_stiction < INFINITY &&
                    fabs(P.foot_radius) < INFINITY && P.max_substep < INFINITY && fabs(P.fall_height) < INFINITY;
   if (!fin || !(P.stiffness > 0) || !(P.dissipation >= 0) || !(P.mu > 0) || !(P.v_stiction > 0) || !(P.tau_max > 0) || !(P.max_substep > 0))
-    return gmisuse("wbc_ground_create: stiffness, mu, v_stiction, tau_max and max_substep must be positive, dissipation non-negative, "
-                   "and all but tau_max finite");
-  WBC_ON_DEVICE(device, gfail);
+    return wbc::plant_misuse("wbc_ground_create: stiffness, mu, v_stiction, tau_max and max_substep must be positive, dissipation "
+                             "non-negative, and all but tau_max finite");
   wbc::ModelC* d = nullptr;
-  GROUND_TRY(hipMalloc(&d, sizeof m));
-  const hipError_t e = hipMemcpy(d, &m, sizeof m, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d);
-    return gfail("hipMemcpy(model)", e);
-  }
+  rc = wbc::plant_model_upload(device, m, &d);
+  if (rc) return rc;
   wbc_ground g = new wbc_ground_s();
   g->device = device;
   g->params = P;
@@ -404,7 +342,7 @@ int wbc_ground_forward(wbc_ground g, void* hip_stream, int n, int ld, const doub
   const int rc = check_ground_args("wbc_ground_forward", g, n, ld, q, v, tau);
   if (rc) return rc;
   if (n == 0) return 0;
-  WBC_ON_DEVICE(g->device, gfail);
+  WBC_ON_DEVICE(g->device, wbc::plant_fail);
   // the forward kernel never writes q or v
   return launch_ground(g, (hipStream_t)hip_stream, false,
                        make_args(g, n, ld, 1, 0.0, const_cast<double*>(q), const_cast<double*>(v), nullptr, tau, mu, mass_scale,
@@ -419,7 +357,7 @@ int wbc_ground_step(wbc_ground g, void* hip_stream, int n, int ld, double dt, do
   const int sub = substeps_for("wbc_ground_step", g, dt);
   if (sub < 0) return sub;
   if (n == 0) return 0;
-  WBC_ON_DEVICE(g->device, gfail);
+  WBC_ON_DEVICE(g->device, wbc::plant_fail);
   return launch_ground(g, (hipStream_t)hip_stream, true,
                        make_args(g, n, ld, sub, dt, q, v, time, tau, mu, mass_scale, ext_wrench, nullptr, force, contact, flags, counts));
 }
@@ -428,59 +366,39 @@ int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stre
                        double* v, double* time, double* targets, uint8_t* contact_mask, const double* mu, const double* mass_scale,
                        const double* ground_mu, const double* ground_mass_scale, const double* ext_wrench, double* tau,
                        double* metrics, int32_t* status, double* force, uint8_t* contact, int32_t* flags, int32_t* counts) {
-  int rc = check_ground_args("wbc_ground_rollout", g, n, ld, q, v, tau);
+  const int rc = check_ground_args("wbc_ground_rollout", g, n, ld, q, v, tau);
   if (rc) return rc;
-  if (!h || !traj) return gmisuse("wbc_ground_rollout: null controller or trajectory handle");
-  if (steps < 0) return gmisuse("wbc_ground_rollout: steps must be >= 0");
-  if (n > 0 && (!time || !targets || !contact_mask)) return gmisuse("wbc_ground_rollout: time, targets and contact_mask are required");
+  if (!h || !traj) return wbc::plant_misuse("wbc_ground_rollout: null controller or trajectory handle");
+  if (steps < 0) return wbc::plant_misuse("wbc_ground_rollout: steps must be >= 0");
+  if (n > 0 && (!time || !targets || !contact_mask)) return wbc::plant_misuse("wbc_ground_rollout: time, targets and contact_mask are required");
   const int sub = substeps_for("wbc_ground_rollout", g, dt);
   if (sub < 0) return sub;
-  // a host-pointer handle is refused by wbc_integrate before anything is launched (n = 0: an argument check only)
-  if (wbc_integrate(h, 0, 0, 0.0, nullptr, nullptr, nullptr)) return gmisuse("wbc_ground_rollout: needs a WBC_DEVICE_PTRS controller handle");
-  if (steps == 0 || n == 0) return 0;
-  rc = wbc_set_stream(h, hip_stream);
-  if (rc) return rc;
-  WBC_ON_DEVICE(g->device, gfail);
   const GroundArgs a = make_args(g, n, ld, sub, dt, q, v, time, tau, ground_mu, ground_mass_scale, ext_wrench, nullptr, force, contact,
                                  flags, counts);
-  for (int s = 0; s < steps; s++) {
-    rc = wbc_traj_lookup(traj, hip_stream, n, ld, time, targets, contact_mask);
-    if (rc) return rc;
-    rc = wbc_step(h, n, ld, q, v, targets, contact_mask, mu, mass_scale, tau, metrics, status);
-    if (rc) return rc;
-    rc = launch_ground(g, (hipStream_t)hip_stream, true, a);
-    if (rc) return rc;
-  }
-  return 0;
+  return wbc::plant_rollout("wbc_ground_rollout", h, traj, g->device, hip_stream, steps, n, ld, q, v, time, targets, contact_mask, mu,
+                            mass_scale, tau, metrics, status, [&] { return launch_ground(g, (hipStream_t)hip_stream, true, a); });
 }
 
 int wbc_ground_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
-  if (!g) return gmisuse("wbc_ground_kernel_info: null ground handle");
-  WBC_ON_DEVICE(g->device, gfail);
-  hipFuncAttributes fa;
-  GROUND_TRY(hipFuncGetAttributes(&fa, (const void*)wbc_ground_step_kernel));
-  if (num_vgpr) *num_vgpr = fa.numRegs;
-  if (scratch_bytes) *scratch_bytes = (int)fa.localSizeBytes;
-  if (lds_bytes) *lds_bytes = (int)fa.sharedSizeBytes;
-  if (block_threads) *block_threads = GROUND_BLOCK;
-  return 0;
+  if (!g) return wbc::plant_misuse("wbc_ground_kernel_info: null ground handle");
+  return WBC_PLANT_KERNEL_INFO(g->device, wbc_ground_step_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
 }
 
 int wbc_terrain_check(const wbc_terrain_profile* profiles, int count) {
   char b[256];
-  if (!profiles) return gmisuse("wbc_terrain_check: null profiles");
-  if (count < 1 || count > WBC_GROUND_MAX_PROFILES) return gmisuse("wbc_terrain_check: count must be 1 .. WBC_GROUND_MAX_PROFILES (16)");
+  if (!profiles) return wbc::plant_misuse("wbc_terrain_check: null profiles");
+  if (count < 1 || count > WBC_GROUND_MAX_PROFILES) return wbc::plant_misuse("wbc_terrain_check: count must be 1 .. WBC_GROUND_MAX_PROFILES (16)");
   for (int p = 0; p < count; p++) {
     const wbc_terrain_profile& t = profiles[p];
     const char* what = wbc::terrain_profile_error(t.nk, t.x0, t.y0, t.yaw, t.s, t.h);
-    if (what) { snprintf(b, sizeof b, "wbc_terrain_check: profile %d: %s", p, what); return gmisuse(b); }
+    if (what) { snprintf(b, sizeof b, "wbc_terrain_check: profile %d: %s", p, what); return wbc::plant_misuse(b); }
   }
   return 0;
 }
 
 int wbc_ground_set_terrain(wbc_ground g, const wbc_terrain_profile* profiles, int count, const uint8_t* terrain_id,
                            const double* terrain_scale) {
-  if (!g) return gmisuse("wbc_ground_set_terrain: null ground handle");
+  if (!g) return wbc::plant_misuse("wbc_ground_set_terrain: null ground handle");
   if (!profiles || count == 0) {
     g->terrain = TerrainArgs{};
     return 0;
@@ -493,11 +411,11 @@ int wbc_ground_set_terrain(wbc_ground g, const wbc_terrain_profile* profiles, in
     const wbc_terrain_profile& t = profiles[p];
     wbc::terrain_pack(t.nk, t.x0, t.y0, t.yaw, t.s, t.h, table + p * wbc::TERRAIN_STRIDE);
   }
-  WBC_ON_DEVICE(g->device, gfail);
-  if (!g->d_terrain) GROUND_TRY(hipMalloc(&g->d_terrain, sizeof table));
-  GROUND_TRY(hipDeviceSynchronize());   // a launch still reading the previous table
+  WBC_ON_DEVICE(g->device, wbc::plant_fail);
+  if (!g->d_terrain) WBC_PLANT_TRY(hipMalloc(&g->d_terrain, sizeof table));
+  WBC_PLANT_TRY(hipDeviceSynchronize());   // a launch still reading the previous table
   g->terrain = TerrainArgs{};
-  GROUND_TRY(hipMemcpy(g->d_terrain, table, (size_t)count * wbc::TERRAIN_STRIDE * sizeof(double), hipMemcpyHostToDevice));
+  WBC_PLANT_TRY(hipMemcpy(g->d_terrain, table, (size_t)count * wbc::TERRAIN_STRIDE * sizeof(double), hipMemcpyHostToDevice));
   g->terrain.table = g->d_terrain;
   g->terrain.id = terrain_id;
   g->terrain.scale = terrain_scale;
@@ -506,15 +424,8 @@ int wbc_ground_set_terrain(wbc_ground g, const wbc_terrain_profile* profiles, in
 }
 
 int wbc_ground_terrain_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
-  if (!g) return gmisuse("wbc_ground_terrain_kernel_info: null ground handle");
-  WBC_ON_DEVICE(g->device, gfail);
-  hipFuncAttributes fa;
-  GROUND_TRY(hipFuncGetAttributes(&fa, (const void*)wbc_ground_terrain_step_kernel));
-  if (num_vgpr) *num_vgpr = fa.numRegs;
-  if (scratch_bytes) *scratch_bytes = (int)fa.localSizeBytes;
-  if (lds_bytes) *lds_bytes = (int)fa.sharedSizeBytes;
-  if (block_threads) *block_threads = GROUND_BLOCK;
-  return 0;
+  if (!g) return wbc::plant_misuse("wbc_ground_terrain_kernel_info: null ground handle");
+  return WBC_PLANT_KERNEL_INFO(g->device, wbc_ground_terrain_step_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
 }
 
 }  // extern "C"

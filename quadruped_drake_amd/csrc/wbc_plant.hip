@@ -9,34 +9,16 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <string.h>
 
 #include "../../include/wbc.h"
 #include "../../include/wbc_plant.h"
 #include "wbc_model.hpp"
 #include "wbc_tick.hpp"
 #include "wbc_plant.hpp"
-#include "wbc_device_guard.hpp"
-
-extern "C" void wbc_set_error_(const char* msg);   // wbc_kernels.hip: the buffer wbc_last_error() returns
+#include "wbc_quad.hpp"
+#include "wbc_plant_host.hpp"
 
 namespace {
-
-int pfail(const char* what, hipError_t e) {
-  char b[512];
-  snprintf(b, sizeof b, "%s: %s", what, hipGetErrorString(e));
-  wbc_set_error_(b);
-  return -2;
-}
-int pmisuse(const char* what) { wbc_set_error_(what); return -1; }
-#define PLANT_TRY(x)                                \
-  do {                                              \
-    hipError_t e_ = (x);                            \
-    if (e_ != hipSuccess) return pfail(#x, e_);     \
-  } while (0)
-
-constexpr int PLANT_BLOCK = 64;   // one wavefront per workgroup: 16 robots
 
 struct PlantArgs {
   int n, ld;
@@ -55,25 +37,6 @@ struct PlantArgs {
   double Kd, tau_max, mu0;
 };
 
-// quad_perm DPP move of a double: CTRL = p0 | p1 << 2 | p2 << 4 | p3 << 6 (lane j of the quad reads lane p_j)
-template <int CTRL> __device__ __forceinline__ double qmove(double x) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-template <int CTRL> __device__ __forceinline__ int qmove_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, false); }
-constexpr int QP_XOR1 = 0xB1, QP_XOR2 = 0x4E;                 // [1 0 3 2], [2 3 0 1]
-template <int K> constexpr int qp_bcast() { return K * 0x55; }  // [K K K K]
-// sum over the quad, the same bits on every lane: (x0 + x1) + (x2 + x3)
-__device__ __forceinline__ double qsum(double x) {
-  const double a = x + qmove<QP_XOR1>(x);
-  return a + qmove<QP_XOR2>(a);
-}
-__device__ __forceinline__ int qor(int x) {
-  const int a = x | qmove_i<QP_XOR1>(x);
-  return a | qmove_i<QP_XOR2>(a);
-}
-
 // Lambda^-1 assembly on every lane: lane c holds its row blocks blk[d] = Z_c' Z_d (+ G_c on the diagonal); block (c, d), d <= c,
 // is broadcast from lane c into the packed lower triangle.
 template <int C> __device__ __forceinline__ void gather_rows(const double (&blk)[4][9], const double* e, double* A, double* eall) {
@@ -83,15 +46,15 @@ template <int C> __device__ __forceinline__ void gather_rows(const double (&blk)
     for (int i = 0; i < 3; i++)
 #pragma unroll
       for (int j = 0; j < 3; j++)
-        if (d < C || j <= i) A[wbc::sp(3 * C + i, 3 * d + j)] = qmove<qp_bcast<C>()>(blk[d][3 * i + j]);
+        if (d < C || j <= i) A[wbc::sp(3 * C + i, 3 * d + j)] = wbc::qmove<wbc::qp_bcast<C>()>(blk[d][3 * i + j]);
 #pragma unroll
-  for (int i = 0; i < 3; i++) eall[3 * C + i] = qmove<qp_bcast<C>()>(e[i]);
+  for (int i = 0; i < 3; i++) eall[3 * C + i] = wbc::qmove<wbc::qp_bcast<C>()>(e[i]);
 }
 
 template <bool STEP>
 __device__ __forceinline__ void plant_body(const wbc::ModelC* __restrict__ mp, const PlantArgs& a) {
   using namespace wbc;
-  const int t = blockIdx.x * PLANT_BLOCK + threadIdx.x;
+  const int t = blockIdx.x * QUAD_BLOCK + threadIdx.x;
   const int l = t & 3;
   const int r = t >> 2;
   const bool live = r < a.n;
@@ -247,10 +210,10 @@ __device__ __forceinline__ void plant_body(const wbc::ModelC* __restrict__ mp, c
 }  // namespace
 
 // stable kernel names (rocprofv3 --kernel-trace)
-__global__ void __launch_bounds__(PLANT_BLOCK) wbc_plant_step_kernel(const wbc::ModelC* __restrict__ m, PlantArgs a) {
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_plant_step_kernel(const wbc::ModelC* __restrict__ m, PlantArgs a) {
   plant_body<true>(m, a);
 }
-__global__ void __launch_bounds__(PLANT_BLOCK) wbc_plant_forward_kernel(const wbc::ModelC* __restrict__ m, PlantArgs a) {
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_plant_forward_kernel(const wbc::ModelC* __restrict__ m, PlantArgs a) {
   plant_body<false>(m, a);
 }
 
@@ -263,22 +226,16 @@ struct wbc_plant_s {
 namespace {
 
 int check_plant_args(const char* fn, wbc_plant p, int n, int ld, const void* q, const void* v, const void* tau, const void* mask) {
-  char b[256];
-  if (n < 0 || n > WBC_MAX_LD) { snprintf(b, sizeof b, "%s: n out of range (0 .. WBC_MAX_LD)", fn); return pmisuse(b); }
-  if (ld > WBC_MAX_LD) { snprintf(b, sizeof b, "%s: ld exceeds WBC_MAX_LD", fn); return pmisuse(b); }
-  if (n > 0 && ld < n) { snprintf(b, sizeof b, "%s: ld must be >= n", fn); return pmisuse(b); }
-  if (!p) { snprintf(b, sizeof b, "%s: null plant handle", fn); return pmisuse(b); }
-  if (n > 0 && (!q || !v || !tau || !mask)) { snprintf(b, sizeof b, "%s: q, v, tau and contact_mask are required", fn); return pmisuse(b); }
-  return 0;
+  return wbc::plant_check_batch(fn, p, "plant", n, ld, q && v && tau && mask, "q, v, tau and contact_mask");
 }
 
 int launch_plant(wbc_plant p, hipStream_t s, bool step, const PlantArgs& a) {
-  const dim3 grid((unsigned)(((size_t)a.n * 4 + PLANT_BLOCK - 1) / PLANT_BLOCK));
+  const dim3 grid = wbc::plant_grid(a.n), block(wbc::QUAD_BLOCK);
   if (step)
-    hipLaunchKernelGGL(wbc_plant_step_kernel, grid, dim3(PLANT_BLOCK), 0, s, p->d_model, a);
+    hipLaunchKernelGGL(wbc_plant_step_kernel, grid, block, 0, s, p->d_model, a);
   else
-    hipLaunchKernelGGL(wbc_plant_forward_kernel, grid, dim3(PLANT_BLOCK), 0, s, p->d_model, a);
-  PLANT_TRY(hipGetLastError());
+    hipLaunchKernelGGL(wbc_plant_forward_kernel, grid, block, 0, s, p->d_model, a);
+  WBC_PLANT_TRY(hipGetLastError());
   return 0;
 }
 
@@ -296,7 +253,7 @@ PlantArgs make_args(wbc_plant p, int n, int ld, double dt, double* q, double* v,
 extern "C" {
 
 int wbc_plant_params_default(wbc_plant_params* out) {
-  if (!out) return pmisuse("wbc_plant_params_default: null argument");
+  if (!out) return wbc::plant_misuse("wbc_plant_params_default: null argument");
   out->Kd_contact = 100.0;
   out->tau_max = INFINITY;
   out->mu = 1.0;
@@ -304,34 +261,18 @@ int wbc_plant_params_default(wbc_plant_params* out) {
 }
 
 int wbc_plant_create(const wbc_model* model, const wbc_plant_params* params, int device, wbc_plant* out) {
-  if (!model || !out) return pmisuse("wbc_plant_create: null argument");
+  if (!model || !out) return wbc::plant_misuse("wbc_plant_create: null argument");
   wbc::ModelC m;
-  if (wbc::model_from_flat(model->flat, &m)) return pmisuse("wbc_plant_create: joint axes must be axis-aligned");
-  if (!wbc::model_axes_are_xyy(&m))
-    return pmisuse("wbc_plant_create: unsupported kinematic tree -- legs with the abduction joint about +-x and the hip and knee "
-                   "joints about +-y (Mini Cheetah, ANYmal)");
-  bool seen_q[12] = {0}, seen_a[12] = {0};
-  int qp[12], ap[12];
-  for (int i = 0; i < 12; i++) {
-    qp[i] = model->q_perm[i]; ap[i] = model->act_perm[i];
-    if (qp[i] < 0 || qp[i] >= 12 || ap[i] < 0 || ap[i] >= 12 || seen_q[qp[i]] || seen_a[ap[i]])
-      return pmisuse("wbc_plant_create: q_perm/act_perm must be permutations of 0..11");
-    seen_q[qp[i]] = seen_a[ap[i]] = true;
-  }
-  wbc::model_set_perms(&m, qp, ap);
+  int rc = wbc::plant_model("wbc_plant_create", model, &m);
+  if (rc) return rc;
   wbc_plant_params P;
   wbc_plant_params_default(&P);
   if (params) P = *params;
   if (!(P.mu > 0) || !(P.tau_max > 0) || !(P.Kd_contact >= 0) || P.mu == INFINITY || P.Kd_contact == INFINITY)
-    return pmisuse("wbc_plant_create: mu must be positive and finite, tau_max positive, Kd_contact non-negative and finite");
-  WBC_ON_DEVICE(device, pfail);
+    return wbc::plant_misuse("wbc_plant_create: mu must be positive and finite, tau_max positive, Kd_contact non-negative and finite");
   wbc::ModelC* d = nullptr;
-  PLANT_TRY(hipMalloc(&d, sizeof m));
-  const hipError_t e = hipMemcpy(d, &m, sizeof m, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d);
-    return pfail("hipMemcpy(model)", e);
-  }
+  rc = wbc::plant_model_upload(device, m, &d);
+  if (rc) return rc;
   wbc_plant p = new wbc_plant_s();
   p->device = device;
   p->params = P;
@@ -355,7 +296,7 @@ int wbc_plant_forward(wbc_plant p, void* hip_stream, int n, int ld, const double
   const int rc = check_plant_args("wbc_plant_forward", p, n, ld, q, v, tau, contact_mask);
   if (rc) return rc;
   if (n == 0) return 0;
-  WBC_ON_DEVICE(p->device, pfail);
+  WBC_ON_DEVICE(p->device, wbc::plant_fail);
   // the forward kernel never writes q or v
   return launch_plant(p, (hipStream_t)hip_stream, false,
                       make_args(p, n, ld, 0.0, const_cast<double*>(q), const_cast<double*>(v), nullptr, tau, contact_mask, mu,
@@ -368,7 +309,7 @@ int wbc_plant_step(wbc_plant p, void* hip_stream, int n, int ld, double dt, doub
   const int rc = check_plant_args("wbc_plant_step", p, n, ld, q, v, tau, contact_mask);
   if (rc) return rc;
   if (n == 0) return 0;
-  WBC_ON_DEVICE(p->device, pfail);
+  WBC_ON_DEVICE(p->device, wbc::plant_fail);
   return launch_plant(p, (hipStream_t)hip_stream, true,
                       make_args(p, n, ld, dt, q, v, time, tau, contact_mask, mu, mass_scale, vdot, force, flags, counts));
 }
@@ -377,39 +318,19 @@ int wbc_plant_rollout(wbc_handle h, wbc_plant p, wbc_traj traj, void* hip_stream
                       double* v, double* time, double* targets, uint8_t* contact_mask, const double* mu, const double* mass_scale,
                       const double* plant_mu, const double* plant_mass_scale, double* tau, double* metrics, int32_t* status,
                       double* force, int32_t* flags, int32_t* counts) {
-  int rc = check_plant_args("wbc_plant_rollout", p, n, ld, q, v, tau, contact_mask);
+  const int rc = check_plant_args("wbc_plant_rollout", p, n, ld, q, v, tau, contact_mask);
   if (rc) return rc;
-  if (!h || !traj) return pmisuse("wbc_plant_rollout: null controller or trajectory handle");
-  if (steps < 0) return pmisuse("wbc_plant_rollout: steps must be >= 0");
-  if (n > 0 && (!time || !targets)) return pmisuse("wbc_plant_rollout: time and targets are required");
-  // a host-pointer handle is refused by wbc_integrate before anything is launched (n = 0: an argument check only)
-  if (wbc_integrate(h, 0, 0, 0.0, nullptr, nullptr, nullptr)) return pmisuse("wbc_plant_rollout: needs a WBC_DEVICE_PTRS controller handle");
-  if (steps == 0 || n == 0) return 0;
-  rc = wbc_set_stream(h, hip_stream);
-  if (rc) return rc;
-  WBC_ON_DEVICE(p->device, pfail);
+  if (!h || !traj) return wbc::plant_misuse("wbc_plant_rollout: null controller or trajectory handle");
+  if (steps < 0) return wbc::plant_misuse("wbc_plant_rollout: steps must be >= 0");
+  if (n > 0 && (!time || !targets)) return wbc::plant_misuse("wbc_plant_rollout: time and targets are required");
   const PlantArgs a = make_args(p, n, ld, dt, q, v, time, tau, contact_mask, plant_mu, plant_mass_scale, nullptr, force, flags, counts);
-  for (int s = 0; s < steps; s++) {
-    rc = wbc_traj_lookup(traj, hip_stream, n, ld, time, targets, contact_mask);
-    if (rc) return rc;
-    rc = wbc_step(h, n, ld, q, v, targets, contact_mask, mu, mass_scale, tau, metrics, status);
-    if (rc) return rc;
-    rc = launch_plant(p, (hipStream_t)hip_stream, true, a);
-    if (rc) return rc;
-  }
-  return 0;
+  return wbc::plant_rollout("wbc_plant_rollout", h, traj, p->device, hip_stream, steps, n, ld, q, v, time, targets, contact_mask, mu,
+                            mass_scale, tau, metrics, status, [&] { return launch_plant(p, (hipStream_t)hip_stream, true, a); });
 }
 
 int wbc_plant_kernel_info(wbc_plant p, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
-  if (!p) return pmisuse("wbc_plant_kernel_info: null plant handle");
-  WBC_ON_DEVICE(p->device, pfail);
-  hipFuncAttributes fa;
-  PLANT_TRY(hipFuncGetAttributes(&fa, (const void*)wbc_plant_step_kernel));
-  if (num_vgpr) *num_vgpr = fa.numRegs;
-  if (scratch_bytes) *scratch_bytes = (int)fa.localSizeBytes;
-  if (lds_bytes) *lds_bytes = (int)fa.sharedSizeBytes;
-  if (block_threads) *block_threads = PLANT_BLOCK;
-  return 0;
+  if (!p) return wbc::plant_misuse("wbc_plant_kernel_info: null plant handle");
+  return WBC_PLANT_KERNEL_INFO(p->device, wbc_plant_step_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
 }
 
 }  // extern "C"

@@ -79,33 +79,31 @@ def _dev_ptr(a, rows, n, tdt, name, device, optional=False):
     return C.c_void_p(a.data_ptr())
 
 
-class RigidContactPlant:
-    """Forward dynamics of N robots under applied torques, stance feet held by rigid contacts, semi-implicit Euler step.
+def _wbc_model(table, q_perm, act_perm):
+    m = _lib.WbcModel()
+    flat = np.asarray(table["flat"], dtype=np.float64)
+    assert flat.size == 215
+    m.flat[:] = flat.tolist()
+    m.q_perm[:] = list(range(12)) if q_perm is None else [int(x) for x in q_perm]
+    m.act_perm[:] = [int(x) for x in (table.get("act_perm", range(12)) if act_perm is None else act_perm)]
+    return m
 
-    model: name or path (as the controllers take it), or a model table; q_perm / act_perm as in the controllers.
-    kd_contact: the stance rows' velocity gain (the controllers' Kd_contact); tau_max: actuator limit (torques are clipped,
-    CLIP reported); mu: the plant's friction where no per-instance value is given (1.0: the reference's ground)."""
 
-    def __init__(self, model="mini_cheetah", device=0, kd_contact=100.0, tau_max=math.inf, mu=1.0, q_perm=None, act_perm=None):
+class _Plant:
+    """What the two plants share: the model table and its wbc_model, the handle's lifetime, torch's stream, kernel_info's answer.
+    A subclass names its wbc_*_destroy in `_destroy` and sets self._h in its __init__."""
+    _destroy = None
+
+    def _open(self, model, device, q_perm, act_perm):
+        """-> (the bound library, the wbc_model of `model`)"""
         self.table = load_model(model) if isinstance(model, str) else model
         self.device = int(device)
-        L = _L()
-        m = _lib.WbcModel()
-        flat = np.asarray(self.table["flat"], dtype=np.float64)
-        assert flat.size == 215
-        m.flat[:] = flat.tolist()
-        m.q_perm[:] = list(range(12)) if q_perm is None else [int(x) for x in q_perm]
-        m.act_perm[:] = [int(x) for x in (self.table.get("act_perm", range(12)) if act_perm is None else act_perm)]
-        p = WbcPlantParams(float(kd_contact), float(tau_max), float(mu))
-        self.params = p
-        h = C.c_void_p()
-        _lib.check(L.wbc_plant_create(C.byref(m), C.byref(p), self.device, C.byref(h)))
-        self._h = h
-        self._L = L
+        self._L = _L()
+        return self._L, _wbc_model(self.table, q_perm, act_perm)
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.wbc_plant_destroy(self._h)
+            getattr(self._L, self._destroy)(self._h)
             self._h = None
 
     def __del__(self):
@@ -117,6 +115,29 @@ class RigidContactPlant:
     def _stream(self):
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _kernel_info(self, fn):
+        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _lib.check(fn(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
+
+
+class RigidContactPlant(_Plant):
+    """Forward dynamics of N robots under applied torques, stance feet held by rigid contacts, semi-implicit Euler step.
+
+    model: name or path (as the controllers take it), or a model table; q_perm / act_perm as in the controllers.
+    kd_contact: the stance rows' velocity gain (the controllers' Kd_contact); tau_max: actuator limit (torques are clipped,
+    CLIP reported); mu: the plant's friction where no per-instance value is given (1.0: the reference's ground)."""
+
+    _destroy = "wbc_plant_destroy"
+
+    def __init__(self, model="mini_cheetah", device=0, kd_contact=100.0, tau_max=math.inf, mu=1.0, q_perm=None, act_perm=None):
+        L, m = self._open(model, device, q_perm, act_perm)
+        p = WbcPlantParams(float(kd_contact), float(tau_max), float(mu))
+        self.params = p
+        h = C.c_void_p()
+        _lib.check(L.wbc_plant_create(C.byref(m), C.byref(p), self.device, C.byref(h)))
+        self._h = h
 
     def _outs(self, n, out):
         import torch
@@ -160,22 +181,10 @@ class RigidContactPlant:
 
     def kernel_info(self):
         """Registers, scratch bytes per lane, LDS bytes and threads per block of the plant-step kernel."""
-        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        _lib.check(self._L.wbc_plant_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-        return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
+        return self._kernel_info(self._L.wbc_plant_kernel_info)
 
 
-def _wbc_model(table, q_perm, act_perm):
-    m = _lib.WbcModel()
-    flat = np.asarray(table["flat"], dtype=np.float64)
-    assert flat.size == 215
-    m.flat[:] = flat.tolist()
-    m.q_perm[:] = list(range(12)) if q_perm is None else [int(x) for x in q_perm]
-    m.act_perm[:] = [int(x) for x in (table.get("act_perm", range(12)) if act_perm is None else act_perm)]
-    return m
-
-
-class GroundContactPlant:
+class GroundContactPlant(_Plant):
     """Forward dynamics of N robots under applied torques on a compliant half-space z = 0 (include/wbc_ground.h): Hunt-Crossley
     normal force, Coulomb friction regularised below v_stiction, explicit substeps of at most max_substep inside one launch.
 
@@ -183,12 +192,11 @@ class GroundContactPlant:
     stiffness = weight / 1 mm, dissipation = 1 / sqrt(g 1 mm), mu 1.0, v_stiction 0.05 m/s, foot_radius 0, tau_max inf,
     max_substep 0.0625 ms, fall_height 0).  Below v_stiction a loaded foot creeps at up to v_stiction."""
 
+    _destroy = "wbc_ground_destroy"
+
     def __init__(self, model="mini_cheetah", device=0, stiffness=None, dissipation=None, mu=None, v_stiction=None, foot_radius=None,
                  tau_max=None, max_substep=None, fall_height=None, q_perm=None, act_perm=None):
-        self.table = load_model(model) if isinstance(model, str) else model
-        self.device = int(device)
-        L = _L()
-        m = _wbc_model(self.table, q_perm, act_perm)
+        L, m = self._open(model, device, q_perm, act_perm)
         p = WbcGroundParams()
         _lib.check(L.wbc_ground_params_default(C.byref(m), C.byref(p)))
         for k, x in (("stiffness", stiffness), ("dissipation", dissipation), ("mu", mu), ("v_stiction", v_stiction),
@@ -199,14 +207,11 @@ class GroundContactPlant:
         h = C.c_void_p()
         _lib.check(L.wbc_ground_create(C.byref(m), C.byref(p), self.device, C.byref(h)))
         self._h = h
-        self._L = L
         self._terrain = None
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._L.wbc_ground_destroy(self._h)
-            self._h = None
-            self._terrain = None
+        super().close()
+        self._terrain = None
 
     def set_terrain(self, profiles, terrain_id=None, terrain_scale=None):
         """Put the ground of terrain.py under the feet: `profiles`, a list of 1 .. 16 terrain.Profile, or None for the plane z = 0
@@ -238,19 +243,9 @@ class GroundContactPlant:
         if self._terrain is not None and self._terrain[3] is not None and self._terrain[3] < n:
             raise ValueError("terrain_id / terrain_scale hold %d instances, the call has %d" % (self._terrain[3], n))
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def substeps(self, dt):
         """The number of explicit substeps wbc_ground_step takes for a period dt."""
         return max(1, int(math.ceil(float(dt) / self.params.max_substep * (1.0 - 1e-12))))
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _inputs(self, q, v, tau, mu, mass_scale, ext_wrench):
         import torch
@@ -295,15 +290,11 @@ class GroundContactPlant:
 
     def kernel_info(self):
         """Registers, scratch bytes per lane, LDS bytes and threads per block of the ground-step kernel."""
-        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        _lib.check(self._L.wbc_ground_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-        return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
+        return self._kernel_info(self._L.wbc_ground_kernel_info)
 
     def terrain_kernel_info(self):
         """kernel_info() of the step kernel that runs while a terrain is set."""
-        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        _lib.check(self._L.wbc_ground_terrain_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-        return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
+        return self._kernel_info(self._L.wbc_ground_terrain_kernel_info)
 
 
 def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=None, plant_mu=None, plant_mass_scale=None, counts=None,

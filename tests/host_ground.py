@@ -1,12 +1,12 @@
 """ctypes view of tools/libhost_ground.so: the compliant-ground plant math of csrc/wbc_ground.hpp instantiated on the host
 (tests only)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import __graft_entry__ as graft
+from host_plant import _f64, _p, batch
+
 _LIB = None
 PARAM_NAMES = ("stiffness", "dissipation", "mu", "v_stiction", "foot_radius", "tau_max", "max_substep", "fall_height")
 
@@ -14,19 +14,11 @@ PARAM_NAMES = ("stiffness", "dissipation", "mu", "v_stiction", "foot_radius", "t
 def lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_ROOT, "tools", "libhost_ground.so")
-        srcs = [os.path.join(_ROOT, "tools", "host_ground.cpp")] + [
-            os.path.join(_ROOT, "quadruped_drake_amd", "csrc", f) for f in ("wbc_ground.hpp", "wbc_plant.hpp", "wbc_tick.hpp", "wbc_model.hpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(s) for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-ffp-contract=off", "-o", so, srcs[0]])
-        _LIB = C.CDLL(so)
+        _LIB = C.CDLL(graft.build_target("host_ground"))
         _LIB.host_ground_defaults.argtypes = [C.c_void_p, C.c_void_p]
         _LIB.host_ground_batch.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 12)
+        _LIB.host_terrain_batch.argtypes = _LIB.host_ground_batch.argtypes + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     return _LIB
-
-
-def _p(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
 
 
 def defaults(flat):
@@ -37,29 +29,15 @@ def defaults(flat):
     return dict(zip(PARAM_NAMES, out.tolist()))
 
 
-def run(flat, q, v, tau, mu=None, mass_scale=None, ext_wrench=None, params=None, q_perm=None, act_perm=None, dt=None, substeps=0,
-        time=None, counts=None, n=None, out=None):
-    """One force evaluation (dt None) or one step of `substeps` substeps (0: ceil(dt / max_substep)).  params: a dict overriding
-    defaults(flat).  Returns dict(vdot, force, contact, flags[, q, v, time, counts, substeps]) -- copies, inputs untouched.
-    n: the batch size where the arrays are wider (ld = q.shape[1] > n; every 2-D array then has ld columns).  out: a dict of
-    preset vdot / force / contact / flags arrays to write into (for looking at what is left of the padding columns)."""
-    q = np.array(q, dtype=np.float64, order="C"); v = np.array(v, dtype=np.float64, order="C")
-    tau = np.ascontiguousarray(tau, dtype=np.float64)
-    ld = q.shape[1]
-    n = ld if n is None else int(n)
-    assert 0 < n <= ld
-    flat = np.ascontiguousarray(flat, dtype=np.float64)
-    qp = np.ascontiguousarray(range(12) if q_perm is None else q_perm, dtype=np.int32)
-    ap = np.ascontiguousarray(range(12) if act_perm is None else act_perm, dtype=np.int32)
+def call(entry, tail, flat, q, v, tau, mu, mass_scale, ext_wrench, params, q_perm, act_perm, dt, substeps, time, counts, n, out):
+    """run() of this module and of host_terrain: `entry` is host_ground_batch or host_terrain_batch, `tail` the arguments the
+    latter takes after the former's."""
+    flat, q, v, tau, qp, ap, tm, cn, n, ld = batch(flat, q, v, tau, q_perm, act_perm, time, counts, n)
     pr = None
     if params is not None:
         d = defaults(flat); d.update(params)
         pr = np.array([d[k] for k in PARAM_NAMES], dtype=np.float64)
-    mu = None if mu is None else np.ascontiguousarray(mu, dtype=np.float64)
-    ms = None if mass_scale is None else np.ascontiguousarray(mass_scale, dtype=np.float64)
-    we = None if ext_wrench is None else np.ascontiguousarray(ext_wrench, dtype=np.float64)
-    tm = None if time is None else np.array(time, dtype=np.float64)
-    cn = None if counts is None else np.array(counts, dtype=np.int32)
+    mu, ms, we = _f64(mu), _f64(mass_scale), _f64(ext_wrench)
     vd = np.zeros((18, ld)); f = np.zeros((12, ld)); ct = np.zeros(ld, np.uint8); fl = np.zeros(ld, np.int32)
     if out is not None:
         vd, f, ct, fl = out["vdot"], out["force"], out["contact"], out["flags"]
@@ -67,11 +45,20 @@ def run(flat, q, v, tau, mu=None, mass_scale=None, ext_wrench=None, params=None,
         assert ct.dtype == np.uint8 and fl.dtype == np.int32 and all(a.flags.c_contiguous for a in (vd, f, ct, fl))
     for a, rows in ((tau, 12), (we, 6), (cn, 4)):
         assert a is None or a.shape == (rows, ld)
-    rc = lib().host_ground_batch(_p(flat), _p(qp), _p(ap), _p(pr), n, ld, 0 if dt is None else 1, int(substeps),
-                                 0.0 if dt is None else float(dt), _p(q), _p(v), _p(tm), _p(tau), _p(mu), _p(ms), _p(we), _p(vd), _p(f),
-                                 _p(ct), _p(fl), _p(cn))
-    assert rc > 0
+    rc = entry(_p(flat), _p(qp), _p(ap), _p(pr), n, ld, 0 if dt is None else 1, int(substeps), 0.0 if dt is None else float(dt),
+               _p(q), _p(v), _p(tm), _p(tau), _p(mu), _p(ms), _p(we), _p(vd), _p(f), _p(ct), _p(fl), _p(cn), *tail)
+    assert rc > 0, rc
     out = dict(vdot=vd, force=f, contact=ct, flags=fl)
     if dt is not None:
         out.update(q=q, v=v, time=tm, counts=cn, substeps=rc)
     return out
+
+
+def run(flat, q, v, tau, mu=None, mass_scale=None, ext_wrench=None, params=None, q_perm=None, act_perm=None, dt=None, substeps=0,
+        time=None, counts=None, n=None, out=None):
+    """One force evaluation (dt None) or one step of `substeps` substeps (0: ceil(dt / max_substep)).  params: a dict overriding
+    defaults(flat).  Returns dict(vdot, force, contact, flags[, q, v, time, counts, substeps]) -- copies, inputs untouched.
+    n: the batch size where the arrays are wider (ld = q.shape[1] > n; every 2-D array then has ld columns).  out: a dict of
+    preset vdot / force / contact / flags arrays to write into (for looking at what is left of the padding columns)."""
+    return call(lib().host_ground_batch, (), flat, q, v, tau, mu, mass_scale, ext_wrench, params, q_perm, act_perm, dt, substeps, time,
+                counts, n, out)

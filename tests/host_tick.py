@@ -5,6 +5,8 @@ import subprocess
 
 import numpy as np
 
+import __graft_entry__ as graft
+
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = None
 _dp = C.POINTER(C.c_double)
@@ -14,20 +16,11 @@ _ip = C.POINTER(C.c_int)
 def lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_ROOT, "tools", "libhost_tick.so")
-        srcs = [os.path.join(_ROOT, "tools", "host_tick.cpp"), os.path.join(_ROOT, "tools", "wbc_scalar_tick.hpp"),
-                os.path.join(_ROOT, "quadruped_drake_amd", "csrc", "wbc_tick.hpp"),
-                os.path.join(_ROOT, "quadruped_drake_amd", "csrc", "wbc_model.hpp"),
-                os.path.join(_ROOT, "quadruped_drake_amd", "csrc", "wbc_hex.hpp"),
-                os.path.join(_ROOT, "quadruped_drake_amd", "csrc", "wbc_traj_dev.hpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(s) for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++20", "-pthread", "-fPIC", "-shared", "-ffp-contract=off",
-                                   "-o", so, srcs[0]])
-        _LIB = C.CDLL(so)
+        _LIB = C.CDLL(graft.build_target("host_tick"))
     return _LIB
 
 
-def build_variant(tmp_path, name, flags, compiler="g++"):
+def build_variant(tmp_path, name, flags, compiler=None):
     """A host instantiation of the kernel headers with the CLOSED alternatives available again (the -DWBC_... switches that round 6 removed from
     the product source: tools/lab/patches/closed_switches.patch re-introduces them): the sources are copied to `tmp_path`, patched there and
     compiled with `flags`.  Without flags the patched tree is the product's code, so a comparison against the default build is a comparison
@@ -45,8 +38,7 @@ def build_variant(tmp_path, name, flags, compiler="g++"):
     subprocess.check_call(["patch", "-p1", "-s", "--no-backup-if-mismatch", "-i", os.path.join(_ROOT, "tools", "lab", "patches", "closed_switches.patch")], cwd=tree)
     so = os.path.join(str(tmp_path), name)
     # HOST_TICK_HEX_ONLY: the 16-lane emulation alone (host_hex_batch is all a variant is asked) -- half the compile time of the full tool
-    subprocess.check_call([compiler, "-O2", "-std=c++20", "-pthread", "-fPIC", "-shared", "-ffp-contract=off", "-DHOST_TICK_HEX_ONLY"] + list(flags) +
-                          ["-o", so, os.path.join(tree, "tools", "host_tick.cpp")])
+    graft.host_shared(so, [os.path.join(tree, "tools", "host_tick.cpp")], ["-pthread", "-DHOST_TICK_HEX_ONLY"] + list(flags), compiler)
     return C.CDLL(so)
 
 

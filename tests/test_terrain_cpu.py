@@ -163,7 +163,7 @@ def test_rotating_the_world_about_z_rotates_the_answer(cfg, model):
 
 
 def test_no_profiles_is_the_flat_host_bit_for_bit():
-    """The tool without a terrain runs the flat instantiation: the bits of tools/host_ground.cpp (on the device: a terrain set and
+    """The tool without a terrain runs the flat instantiation: the bits of host_ground_batch (on the device: a terrain set and
     cleared against a fresh handle, tests/test_terrain_gpu.py)."""
     t, q, v, tau, sp, we = go.draw(3, 48, 63)
     for dt in (None, 1e-3):

@@ -1,52 +1,30 @@
 // host_plant.cpp -- TEST TOOL, not product code.
 // Instantiates the plant math (quadruped_drake_amd/csrc/wbc_plant.hpp) on the host with `double`: the same phases the device
 // kernel runs on the four lanes of a quad, here one leg after the other, with the quad sums as plain sums in the kernel's order
-// ((leg0 + leg1) + (leg2 + leg3)).  tests/host_plant.py builds it; the shipped library never calls it.
+// ((leg0 + leg1) + (leg2 + leg3)).  tests/host_plant.py loads it; the shipped library never calls it.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
-#include "../quadruped_drake_amd/csrc/wbc_model.hpp"
-#include "../quadruped_drake_amd/csrc/wbc_plant.hpp"
+#include "host_batch.hpp"
 
 using namespace wbc;
-
-static double qsum4(const double* x) { return (x[0] + x[1]) + (x[2] + x[3]); }
 
 // one instance; q, v in place when step != 0
 static void plant_one(const ModelC& m, double Kd, double tau_max, double mu0, int i, size_t ld, int step, double dt, double* q,
                       double* v, double* time, const double* tau, const uint8_t* maskp, const double* mup, const double* msp,
                       double* vdot, double* force, int32_t* flags, int32_t* counts) {
-  double qb[7], vb[6], th[4][3], qd[4][3], tq[4][3];
-  int qrow[4][3];
-  for (int k = 0; k < 7; k++) qb[k] = q[k * ld + i];
-  for (int k = 0; k < 6; k++) vb[k] = v[k * ld + i];
-  for (int l = 0; l < 4; l++)
-    for (int k = 0; k < 3; k++) {
-      qrow[l][k] = m.q_perm[3 * l + k];
-      th[l][k] = q[(7 + qrow[l][k]) * ld + i];
-      qd[l][k] = v[(6 + qrow[l][k]) * ld + i];
-      tq[l][k] = tau[m.act_inv[3 * l + k] * ld + i];
-    }
+  HostInstance s;
+  host_gather(m, i, ld, q, v, tau, s);
   const unsigned mask = maskp[i] & 15u;
   const double mu = mup ? mup[i] : mu0, s_p = msp ? msp[i] : 1.0;
-  int bits = 0;
-  bool nf = false, clip = false;
-  for (int k = 0; k < 7; k++) nf |= not_finite(qb[k]);
-  for (int k = 0; k < 6; k++) nf |= not_finite(vb[k]);
-  double ta[4][3];
-  for (int l = 0; l < 4; l++)
-    for (int k = 0; k < 3; k++) {
-      nf |= not_finite(th[l][k]) | not_finite(qd[l][k]) | not_finite(tq[l][k]);
-      clip |= fabs(tq[l][k]) > tau_max * (1.0 + PLANT_CLIP_TOL);
-      ta[l][k] = fmin(fmax(tq[l][k], -tau_max), tau_max);
-    }
-  nf |= !(mu > 0.0) | not_finite(mu) | !(s_p > 0.0) | not_finite(s_p);
-  bits = (nf ? PLANT_BAD : 0) | (clip ? PLANT_CLIP : 0);
+  bool clip;
+  bool nf = host_check_inputs(s, tau_max, mu, s_p, clip);
+  int bits = (nf ? PLANT_BAD : 0) | (clip ? PLANT_CLIP : 0);
   double R0[9];
-  plant_rotation(qb, R0);
-  const double w0[3] = {vb[0], vb[1], vb[2]}, v0[3] = {vb[3], vb[4], vb[5]};
+  plant_rotation(s.qb, R0);
+  const double w0[3] = {s.vb[0], s.vb[1], s.vb[2]}, v0[3] = {s.vb[3], s.vb[4], s.vb[5]};
   PlantLeg<double> L[4];
-  for (int l = 0; l < 4; l++) plant_leg_phase1(m, l, R0, w0, v0, th[l], qd[l], ta[l], ((mask >> l) & 1u) != 0, Kd, L[l]);
+  for (int l = 0; l < 4; l++) plant_leg_phase1(m, l, R0, w0, v0, s.th[l], s.qd[l], s.ta[l], ((mask >> l) & 1u) != 0, Kd, L[l]);
   double S[27];
   plant_base_share(m, R0, w0, s_p, S);
   for (int k = 0; k < 27; k++) {
@@ -93,30 +71,16 @@ static void plant_one(const ModelC& m, double Kd, double tau_max, double mu0, in
       f[3 * l + k] = (bad || !((mask >> l) & 1u)) ? 0.0 : f[3 * l + k];
     }
   if (flags) flags[i] = bits;
-  if (vdot) {
-    for (int k = 0; k < 6; k++) vdot[k * ld + i] = vdb[k];
-    for (int l = 0; l < 4; l++)
-      for (int k = 0; k < 3; k++) vdot[(6 + qrow[l][k]) * ld + i] = vdl[l][k];
-  }
+  if (vdot) host_store_vdot(s, i, ld, bad, vdb, vdl, vdot);
   if (force)
     for (int k = 0; k < 12; k++) force[k * ld + i] = f[k];
   if (!step) return;
   if (!bad) {
-    plant_integrate_base(dt, vdb, qb, vb);
-    for (int k = 0; k < 6; k++) v[k * ld + i] = vb[k];
-    for (int k = 0; k < 7; k++) q[k * ld + i] = qb[k];
+    plant_integrate_base(dt, vdb, s.qb, s.vb);
     for (int l = 0; l < 4; l++)
-      for (int k = 0; k < 3; k++) {
-        double qn = th[l][k], vn = qd[l][k];
-        plant_integrate_joint(dt, vdl[l][k], qn, vn);
-        v[(6 + qrow[l][k]) * ld + i] = vn;
-        q[(7 + qrow[l][k]) * ld + i] = qn;
-      }
+      for (int k = 0; k < 3; k++) plant_integrate_joint(dt, vdl[l][k], s.th[l][k], s.qd[l][k]);
   }
-  if (time) time[i] += dt;
-  if (counts)
-    for (int b = 0; b < 4; b++)
-      if ((bits >> b) & 1) counts[b * ld + i] += 1;
+  host_store_step(s, i, ld, bad, dt, bits, q, v, time, counts);
 }
 
 extern "C" {

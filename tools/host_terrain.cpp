@@ -1,169 +1,4 @@
 // host_terrain.cpp -- TEST TOOL, not product code.
-// The compliant-ground plant math (quadruped_drake_amd/csrc/wbc_ground.hpp) on the host with `double`, as tools/host_ground.cpp,
-// with the TERRAIN instantiation of the force law: the packed terrain table the device kernels stage in LDS lives in plain memory
-// here, and the phases the kernel runs on the four lanes of a quad run one leg after the other, with the quad sums as plain sums
-// in the kernel's order ((leg0 + leg1) + (leg2 + leg3)).  profiles == NULL runs the flat instantiation (the arithmetic of
-// tools/host_ground.cpp).  tests/host_terrain.py builds it; the shipped library never calls it.
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
-#include "../include/wbc_ground.h"
-#include "../quadruped_drake_amd/csrc/wbc_model.hpp"
-#include "../quadruped_drake_amd/csrc/wbc_ground.hpp"
-
-using namespace wbc;
-
-static double qsum4(const double* x) { return (x[0] + x[1]) + (x[2] + x[3]); }
-
-struct HostTerrain {
-  GroundLaw<double> law;
-  double mu0, tau_max, fall_height;
-  int count;                                            // 0: flat
-  double table[TERRAIN_MAX_PROFILES * TERRAIN_STRIDE];
-  const uint8_t* id;
-  const double* scale;
-};
-
-// one instance; `substeps` force evaluations, each followed by an Euler step of h when step != 0 (q, v in place)
-template <bool TERRAIN>
-static void terrain_one(const ModelC& m, const HostTerrain& P, int i, size_t ld, int step, int substeps, double dt, double* q, double* v,
-                        double* time, const double* tau, const double* mup, const double* msp, const double* wext, double* vdot,
-                        double* force, uint8_t* contact, int32_t* flags, int32_t* counts) {
-  double qb[7], vb[6], th[4][3], qd[4][3], tq[4][3], ta[4][3], we[6];
-  int qrow[4][3];
-  for (int k = 0; k < 7; k++) qb[k] = q[k * ld + i];
-  for (int k = 0; k < 6; k++) vb[k] = v[k * ld + i];
-  for (int k = 0; k < 6; k++) we[k] = wext ? wext[k * ld + i] : 0.0;
-  for (int l = 0; l < 4; l++)
-    for (int k = 0; k < 3; k++) {
-      qrow[l][k] = m.q_perm[3 * l + k];
-      th[l][k] = q[(7 + qrow[l][k]) * ld + i];
-      qd[l][k] = v[(6 + qrow[l][k]) * ld + i];
-      tq[l][k] = tau[m.act_inv[3 * l + k] * ld + i];
-    }
-  const double mu = mup ? mup[i] : P.mu0, s_p = msp ? msp[i] : 1.0;
-  bool nf = false, clip = false;
-  for (int k = 0; k < 7; k++) nf |= not_finite(qb[k]);
-  for (int k = 0; k < 6; k++) nf |= not_finite(vb[k]) | not_finite(we[k]);
-  for (int l = 0; l < 4; l++)
-    for (int k = 0; k < 3; k++) {
-      nf |= not_finite(th[l][k]) | not_finite(qd[l][k]) | not_finite(tq[l][k]);
-      clip |= fabs(tq[l][k]) > P.tau_max * (1.0 + PLANT_CLIP_TOL);
-      ta[l][k] = fmin(fmax(tq[l][k], -P.tau_max), P.tau_max);
-    }
-  nf |= !(mu > 0.0) | not_finite(mu) | !(s_p > 0.0) | not_finite(s_p);
-  const double* tab = nullptr;
-  double tscale = 1.0;
-  if (TERRAIN) {
-    const int id = P.id ? (int)P.id[i] : 0;
-    tscale = P.scale ? P.scale[i] : 1.0;
-    const bool tbad = id >= P.count || not_finite(tscale);
-    nf |= tbad;
-    tab = P.table + (tbad ? 0 : id) * TERRAIN_STRIDE;
-  }
-  int bits = clip ? GROUND_CLIP : 0;
-  const double h = step ? dt / substeps : 0.0;
-  double fsum[12] = {0}, vdb[6] = {0}, vdl[4][3] = {{0}};
-  int touch = 0, slip = 0;
-  for (int s = 0; s < substeps; s++) {
-    double R0[9];
-    plant_rotation(qb, R0);
-    const double w0[3] = {vb[0], vb[1], vb[2]}, v0[3] = {vb[3], vb[4], vb[5]};
-    PlantLeg<double> L[4];
-    double f[12];
-    touch = 0;
-    for (int l = 0; l < 4; l++) {
-      const int fb = ground_leg_phase<TERRAIN>(m, l, R0, w0, v0, qb[6], th[l], qd[l], ta[l], P.law, mu, L[l], f + 3 * l, qb[4], qb[5], tab, tscale);
-      touch |= (fb & GROUND_FOOT_TOUCH) ? (1 << l) : 0;
-      slip |= (fb & GROUND_FOOT_SLIP) ? 1 : 0;
-    }
-    double S[27];
-    plant_base_share(m, R0, w0, s_p, S);
-    for (int k = 0; k < 27; k++) {
-      const double x[4] = {L[0].s[k], L[1].s[k], L[2].s[k], L[3].s[k]};
-      S[k] = S[k] + qsum4(x);
-    }
-    for (int k = 0; k < 6; k++) S[21 + k] = S[21 + k] + we[k];
-    ground_base_solve(S, vdb);
-    for (int l = 0; l < 4; l++) plant_leg_final(L[l], vdb, f + 3 * l, vdl[l]);
-    for (int k = 0; k < 6; k++) nf |= not_finite(vdb[k]);
-    for (int l = 0; l < 4; l++)
-      for (int k = 0; k < 3; k++) nf |= not_finite(vdl[l][k]) | not_finite(f[3 * l + k]);
-    for (int k = 0; k < 12; k++) fsum[k] += f[k];
-    if (step) {
-      plant_integrate_base(h, vdb, qb, vb);
-      for (int l = 0; l < 4; l++)
-        for (int k = 0; k < 3; k++) plant_integrate_joint(h, vdl[l][k], th[l][k], qd[l][k]);
-    }
-  }
-  for (int k = 0; k < 7; k++) nf |= not_finite(qb[k]);
-  bits |= nf ? GROUND_BAD : 0;
-  const bool bad = nf;
-  if (!bad) bits |= (slip ? GROUND_SLIP : 0) | (ground_fell<TERRAIN>(qb, P.fall_height, tab, tscale) ? GROUND_FELL : 0);
-  if (flags) flags[i] = bits;
-  if (contact) contact[i] = bad ? 0 : (uint8_t)touch;
-  if (vdot) {
-    for (int k = 0; k < 6; k++) vdot[k * ld + i] = bad ? 0.0 : vdb[k];
-    for (int l = 0; l < 4; l++)
-      for (int k = 0; k < 3; k++) vdot[(6 + qrow[l][k]) * ld + i] = bad ? 0.0 : vdl[l][k];
-  }
-  const double inv = 1.0 / substeps;
-  if (force)
-    for (int k = 0; k < 12; k++) force[k * ld + i] = bad ? 0.0 : fsum[k] * inv;
-  if (!step) return;
-  if (!bad) {
-    for (int k = 0; k < 6; k++) v[k * ld + i] = vb[k];
-    for (int k = 0; k < 7; k++) q[k * ld + i] = qb[k];
-    for (int l = 0; l < 4; l++)
-      for (int k = 0; k < 3; k++) {
-        v[(6 + qrow[l][k]) * ld + i] = qd[l][k];
-        q[(7 + qrow[l][k]) * ld + i] = th[l][k];
-      }
-  }
-  if (time) time[i] += dt;
-  if (counts)
-    for (int b = 0; b < 4; b++)
-      if ((bits >> b) & 1) counts[b * ld + i] += 1;
-}
-
-extern "C" {
-
-// The arguments of host_ground_batch (tools/host_ground.cpp), then the terrain as wbc_ground_set_terrain takes it, with host
-// pointers.  profiles NULL or count 0: no terrain.  Returns the number of substeps, < 0 on a malformed model or terrain.
-int host_terrain_batch(const double* flat215, const int* q_perm, const int* act_perm, const double* params8, int n, int ld, int step,
-                       int substeps, double dt, double* q, double* v, double* time, const double* tau, const double* mu,
-                       const double* mass_scale, const double* ext_wrench, double* vdot, double* force, uint8_t* contact,
-                       int32_t* flags, int32_t* counts, const wbc_terrain_profile* profiles, int count, const uint8_t* terrain_id,
-                       const double* terrain_scale) {
-  ModelC m;
-  if (model_from_flat(flat215, &m) || !model_axes_are_xyy(&m)) return -1;
-  model_set_perms(&m, q_perm, act_perm);
-  double p8[8];
-  ground_default_law(m, &p8[0], &p8[1]);
-  p8[2] = 1.0; p8[3] = GROUND_V_STICTION; p8[4] = 0.0; p8[5] = INFINITY; p8[6] = GROUND_MAX_SUBSTEP; p8[7] = 0.0;
-  if (params8) memcpy(p8, params8, sizeof p8);
-  HostTerrain P;
-  P.law.k = p8[0]; P.law.d = p8[1]; P.mu0 = p8[2]; P.law.vs = p8[3]; P.law.radius = p8[4]; P.tau_max = p8[5]; P.fall_height = p8[7];
-  P.count = 0; P.id = terrain_id; P.scale = terrain_scale;
-  if (profiles && count != 0) {
-    if (count < 1 || count > TERRAIN_MAX_PROFILES) return -2;
-    for (int p = 0; p < count; p++) {
-      const wbc_terrain_profile& t = profiles[p];
-      if (terrain_profile_error(t.nk, t.x0, t.y0, t.yaw, t.s, t.h)) return -2;
-      terrain_pack(t.nk, t.x0, t.y0, t.yaw, t.s, t.h, P.table + p * TERRAIN_STRIDE);
-    }
-    P.count = count;
-  }
-  if (!step) substeps = 1;
-  else if (substeps <= 0) substeps = ground_substeps(dt, p8[6]);
-  if (substeps <= 0) return -1;
-  for (int i = 0; i < n; i++) {
-    if (P.count)
-      terrain_one<true>(m, P, i, (size_t)ld, step, substeps, dt, q, v, time, tau, mu, mass_scale, ext_wrench, vdot, force, contact, flags, counts);
-    else
-      terrain_one<false>(m, P, i, (size_t)ld, step, substeps, dt, q, v, time, tau, mu, mass_scale, ext_wrench, vdot, force, contact, flags, counts);
-  }
-  return substeps;
-}
-
-}  // extern "C"
+// host_terrain_batch lives in host_ground.cpp, beside the flat entry, in tools/libhost_ground.so.  This file keeps the library's
+// former name buildable (g++ ... -o libhost_terrain.so host_terrain.cpp) for a tests/ tree from before the two were one.
+#include "host_ground.cpp"
