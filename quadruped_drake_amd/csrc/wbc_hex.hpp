@@ -27,10 +27,13 @@
 #if !defined(__HIPCC__) && defined(WBC_HOST_GI_STATS)
 extern int g_gi_fast_trips, g_gi_generic_trips, g_gi_drops, g_gi_force_bail;
 extern double* g_gi_dump;   // analysis: [16][NV + 3] per robot = the active set's inputs (own row of J, z, mu_n, inv_s) of every lane
+extern int* g_gi_adds;      // tests: [32] per robot = how many rows the active set added, then their ids in the order of the adds (fast and generic trips)
+#define WBC_GI_ADD(h, row) WBC_GI_STAT(if (g_gi_adds && (h) == 0 && g_gi_adds[0] < 31) g_gi_adds[++g_gi_adds[0]] = (row))
 #define WBC_GI_FORCE_BAIL(qc) (g_gi_force_bail == (qc))
 #define WBC_GI_STAT(x) do { x; } while (0)
 #else
 #define WBC_GI_STAT(x) do { } while (0)
+#define WBC_GI_ADD(h, row) do { } while (0)
 #endif
 // host instantiations (tests, tools/host_tick.cpp) check the kernel's structural invariants; device code carries none of it
 #if !defined(__HIPCC__)
@@ -39,6 +42,8 @@ extern double* g_gi_dump;   // analysis: [16][NV + 3] per robot = the active set
 #else
 #define WBC_HOST_ASSERT(x) do { } while (0)
 #endif
+// block placement: a condition that is almost never true (the exits of the active set's fast chain) -- its code is laid out after the hot path, which falls through
+#define WBC_UNLIKELY(x) __builtin_expect(!!(x), 0)
 #ifndef WBC_GI_FORCE_BAIL
 #ifdef WBC_DEV_FORCE_BAIL   // diagnostic device builds: every wavefront leaves the fast path at trip WBC_DEV_FORCE_BAIL
 #define WBC_GI_FORCE_BAIL(qc) ((qc) == WBC_DEV_FORCE_BAIL)
@@ -306,12 +311,14 @@ WBC_HD int hex_gi(Q& qo, int h, bool ct, double* Jr, double& z, double mu_n, dou
   int ho_p = -1, ho_hd = -1;
   double ho_d[NV], ho_sp = 0.0, ho_dn = 1.0, ho_d2n = 0.0, ho_zd = 0.0, ho_sd = 0.0, ho_r = 0.0, ho_t1 = 0.0;
   if constexpr (QF > 0) {
-    bool stop = false;   // wave-uniform
-    static_for<QF>([&](auto QQ) {
+    // The chain of bodies is NESTED, not a sequence: body qc ends by entering body qc + 1, and every exit is a plain return out of the whole
+    // chain.  (As a sequence with a `stop` flag every body's exit code re-joined in front of the next body's test of the flag: the hot path
+    // jumped over its own exit stubs once per trip, a taken branch of ~100 cycles on a lone wavefront -- profiles/r02/dpp_fmac.md.)
+    auto chain = [&](auto& self, auto QQ) -> void {
       constexpr int qc = QQ;
-      if (stop) return;
       // pick (a finished robot offers no candidate)
       int pf;
+      bool cand;   // the robot has a candidate row
       {
         double key = HEX_NONE;
         if (!done && ct && !act_h && !(APEX && nleg == 3)) {
@@ -330,15 +337,19 @@ WBC_HD int hex_gi(Q& qo, int h, bool ct, double* Jr, double& z, double mu_n, dou
           }
         }
         key = qo.min16(key);
-        pf = (key < 1e299) ? pick_index(key) : -1;
+        cand = key < 1e299;
+        pf = cand ? pick_index(key) : -1;
       }
       // PC law: the dense row (Vdot <= 0) is never added here -- a robot whose dense row is violated sends the wavefront to the
       // generic loop (rare: ~5 % of the robots); while it is inactive the fast trips only carry its image and value along
       const bool pcv = PC && pc && spc < -tol;
       // every wavefront's last trip finds nothing left to repair anywhere: leave before the crossbar round trip
-      if (qo.wave_all(done || (pf < 0 && !pcv))) { done = true; stop = true; generic = false; return; }
+      // (friction-only laws: a finished robot's sixteen keys are HEX_NONE, so `done || !cand` IS `!cand` and the vote is the one compare of the key)
+      WBC_HOST_ASSERT(!done || !cand);
+      if (WBC_UNLIKELY(qo.wave_all(PC ? (done || (!cand && !pcv)) : !cand))) { done = true; generic = false; return; }
       // ONE round trip: the picked row's image, value and norm from its lane (own lane when there is no candidate)
-      const int pl = (pf >= 0) ? pf : h;
+      // (asking for value and norm BEFORE the image, so that the blocking-ratio chain starts under a partial wait, was measured: no gain -- profiles/r11/trip_path.md)
+      const int pl = cand ? pf : h;
       double d[NV];
 #pragma unroll
       for (int k = 0; k < NV; k++) d[k] = qo.bcast16d(Dh[k], pl);
@@ -347,7 +358,7 @@ WBC_HD int hex_gi(Q& qo, int h, bool ct, double* Jr, double& z, double mu_n, dou
       const bool pcpick = pcv && !(pf >= 0 && !(spc < spx));
       if (!(pf >= 0 && spx < -tol) && !pcpick) done = true;        // nothing (left) to repair on this robot
       // (with the gain pick only violated rows are candidates: a robot with a candidate stays live, the test above was the exit)
-      if (!wave_gain_all && qo.wave_all(done)) { stop = true; generic = false; return; }
+      if (WBC_UNLIKELY(!wave_gain_all && qo.wave_all(done))) { generic = false; return; }
       double d2n = 0.0, zd = 0.0, sd = 0.0, r_h = 0.0;
       static_for<NV - qc>([&](auto KK) { constexpr int k = qc + KK; d2n = fmad(d[k], d[k], d2n); });
       static_for<NV - qc>([&](auto KK) { constexpr int k = qc + KK; zd = fmad(Jr[k], d[k], zd); sd = fmad(Dh[k], d[k], sd); });
@@ -366,8 +377,7 @@ WBC_HD int hex_gi(Q& qo, int h, bool ct, double* Jr, double& z, double mu_n, dou
       fast_sqrt_rsq(d2n, nrm, rsn);
       const double t2 = -spx * (rsn * rsn);
       const bool full = !dependent && (!have_t1 || !(t1 < t2));
-      if (qo.wave_any(!done && (!full || pcpick)) || WBC_GI_FORCE_BAIL(qc)) {   // not a friction add-with-full-step everywhere: generic loop, state untouched
-        stop = true;
+      if (WBC_UNLIKELY(qo.wave_any(!done && (!full || pcpick)) || WBC_GI_FORCE_BAIL(qc))) {   // not a friction add-with-full-step everywhere: generic loop, state untouched
         if constexpr (!PC) {   // (measured on the PC law, whose dense row sends ~20 % of the wavefronts here: +2 % -- not taken over there)
           handed = true;
           ho_p = pf; ho_sp = spx; ho_dn = dnx; ho_d2n = d2n; ho_zd = zd; ho_sd = sd; ho_r = r_h;
@@ -380,6 +390,7 @@ WBC_HD int hex_gi(Q& qo, int h, bool ct, double* Jr, double& z, double mu_n, dou
       if (!done) {
         iters++;
         WBC_GI_STAT(if (h == 0) g_gi_fast_trips++);
+        WBC_GI_ADD(h, pf);
         u_h = fmad(-t2, r_h, u_h);
         z = fmad(t2, zd, z);
         sh_ = fmad(t2, sd, sh_);
@@ -408,7 +419,9 @@ WBC_HD int hex_gi(Q& qo, int h, bool ct, double* Jr, double& z, double mu_n, dou
         if (APEX) nleg += same_leg(pf);
         q = qc + 1;
       }
-    });
+      if constexpr (qc + 1 < QF) self(self, std::integral_constant<int, qc + 1>{});
+    };
+    chain(chain, std::integral_constant<int, 0>{});
   }
   // ---- Generic loop.  Position mask kept as doubles (replicated): mk = 1 on the free slots k >= q; the one-hot of the next free
   // slot is eq[k] = mk[k] - mk[k-1].  Products with them replace select chains (d masked, d[q], the reflector).
@@ -691,6 +704,7 @@ WBC_HD int hex_gi(Q& qo, int h, bool ct, double* Jr, double& z, double mu_n, dou
     // append: W' = [W, -r/alpha; 0, 1/alpha]  (rows of inactive lanes are zero, r_h = 0 there; slot q is zero beforehand)
     {
       const bool mine = full && (h == p);
+      if (full) WBC_GI_ADD(h, p);
       const double wq = full ? (mine ? ia : -r_h * ia) : 0.0;
 #pragma unroll
       for (int k = 0; k < NV; k++) Wr[k] = fmad(eq[k], wq, Wr[k]);
