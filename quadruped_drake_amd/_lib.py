@@ -125,3 +125,37 @@ def lib():
 def check(rc):
     if rc != 0:
         raise WbcError("libwbc_hip: rc=%d: %s" % (rc, lib().wbc_last_error().decode()))
+
+
+def fill_model(table, q_perm=None, act_perm=None):
+    """The wbc_model of a model table; q_perm None: the identity, act_perm None: the table's own."""
+    m = WbcModel()
+    assert len(table["flat"]) == 215
+    m.flat[:] = [float(x) for x in table["flat"]]
+    m.q_perm[:] = list(range(12)) if q_perm is None else [int(x) for x in q_perm]
+    m.act_perm[:] = [int(x) for x in (table.get("act_perm", range(12)) if act_perm is None else act_perm)]
+    return m
+
+
+def dev_ptr(a, rows, n, tdt, name, device, owner, optional=False):
+    """Pointer to a contiguous CUDA tensor of dtype tdt and shape [rows, n] ([n] when rows is 0) on cuda:`device`, where `owner`
+    ("the plant", "this controller's handle") lives; None for an absent optional tensor."""
+    import torch
+    if a is None:
+        if optional:
+            return None
+        raise ValueError(name + " is required")
+    if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == tdt and a.is_contiguous()):
+        raise ValueError("%s: expected a contiguous CUDA tensor of dtype %s" % (name, tdt))
+    if a.device.index != device:
+        raise ValueError("%s: tensor lives on cuda:%s, %s on cuda:%d" % (name, a.device.index, owner, device))
+    if tuple(a.shape) != ((rows, n) if rows else (n,)):
+        raise ValueError("%s: expected shape %s, got %s" % (name, (rows, n) if rows else (n,), tuple(a.shape)))
+    return C.c_void_p(a.data_ptr())
+
+
+def kernel_info(fn, handle):
+    """The answer of a wbc_*_kernel_info entry point as a dict"""
+    a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    check(fn(handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)

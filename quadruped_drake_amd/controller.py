@@ -72,12 +72,7 @@ class BatchedController:
         self.device = int(device)
         self.host_ptrs = bool(host_ptrs)
         L = _lib.lib()
-        m = _lib.WbcModel()
-        flat = np.asarray(self.table["flat"], dtype=np.float64)
-        assert flat.size == 215
-        m.flat[:] = flat.tolist()
-        m.q_perm[:] = list(range(12)) if q_perm is None else [int(x) for x in q_perm]
-        m.act_perm[:] = [int(x) for x in (self.table.get("act_perm", range(12)) if act_perm is None else act_perm)]
+        m = _lib.fill_model(self.table, q_perm, act_perm)
         p = _lib.WbcParams()
         _lib.check(L.wbc_params_default(self.kind, C.byref(p)))
         for k, val in (params or {}).items():
@@ -130,13 +125,7 @@ class BatchedController:
             return arr, C.c_void_p(arr.ctypes.data)
         import torch
         tdt = {np.float64: torch.float64, np.uint8: torch.uint8, np.int32: torch.int32}[dtype]
-        if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == tdt and a.is_contiguous()):
-            raise ValueError("%s: expected a contiguous CUDA tensor of dtype %s" % (name, tdt))
-        if a.device.index != self.device:
-            raise ValueError("%s: tensor lives on cuda:%s, this controller's handle on cuda:%d" % (name, a.device.index, self.device))
-        if tuple(a.shape) != ((rows, n) if rows else (n,)):
-            raise ValueError("%s: expected shape %s, got %s" % (name, (rows, n) if rows else (n,), tuple(a.shape)))
-        return a, C.c_void_p(a.data_ptr())
+        return a, _lib.dev_ptr(a, rows, n, tdt, name, self.device, "this controller's handle")
 
     def _out(self, rows, n, dtype):
         if self.host_ptrs:
@@ -305,10 +294,7 @@ class BatchedController:
 
     def kernel_info(self, rollout=False):
         """Registers, scratch bytes per lane and LDS bytes of the tick kernel (rollout=True: of the persistent closed-loop kernel)."""
-        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        fn = self._L.wbc_rollout_kernel_info if rollout else self._L.wbc_kernel_info
-        _lib.check(fn(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-        return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
+        return _lib.kernel_info(self._L.wbc_rollout_kernel_info if rollout else self._L.wbc_kernel_info, self._h)
 
     # -- single-robot convenience with the reference's signature --------------------------
     def ControlLaw(self, q, v, trunk_data):

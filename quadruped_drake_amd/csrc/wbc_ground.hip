@@ -243,9 +243,9 @@ int check_ground_args(const char* fn, wbc_ground g, int n, int ld, const void* q
 
 // the substeps of a period dt; < 0 with the message set when dt is not a positive finite time or needs more than 2^20 substeps
 int substeps_for(const char* fn, wbc_ground g, double dt) {
-  if (!(dt > 0.0) || dt == INFINITY) return wbc::plant_misuse(fn, "dt must be positive and finite");
+  if (!(dt > 0.0) || dt == INFINITY) return wbc::misuse(fn, "dt must be positive and finite");
   const int s = wbc::ground_substeps(dt, g->params.max_substep);
-  if (s <= 0) return wbc::plant_misuse(fn, "dt / max_substep exceeds 2^20 substeps");
+  if (s <= 0) return wbc::misuse(fn, "dt / max_substep exceeds 2^20 substeps");
   return s;
 }
 
@@ -260,7 +260,7 @@ int launch_ground(wbc_ground g, hipStream_t s, bool step, const GroundArgs& a) {
     hipLaunchKernelGGL(wbc_ground_step_kernel, grid, block, 0, s, g->d_model, a);
   else
     hipLaunchKernelGGL(wbc_ground_forward_kernel, grid, block, 0, s, g->d_model, a);
-  WBC_PLANT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -292,18 +292,18 @@ void default_params(const wbc::ModelC& m, wbc_ground_params* out) {
 extern "C" {
 
 int wbc_ground_params_default(const wbc_model* model, wbc_ground_params* out) {
-  if (!model || !out) return wbc::plant_misuse("wbc_ground_params_default: null argument");
+  if (!model || !out) return wbc::misuse("wbc_ground_params_default: null argument");
   wbc::ModelC m;
-  const int rc = wbc::plant_model_axes("wbc_ground_params_default", model, &m);
+  const int rc = wbc::model_axes("wbc_ground_params_default", model, &m);
   if (rc) return rc;
   default_params(m, out);
   return 0;
 }
 
 int wbc_ground_create(const wbc_model* model, const wbc_ground_params* params, int device, wbc_ground* out) {
-  if (!model || !out) return wbc::plant_misuse("wbc_ground_create: null argument");
+  if (!model || !out) return wbc::misuse("wbc_ground_create: null argument");
   wbc::ModelC m;
-  int rc = wbc::plant_model("wbc_ground_create", model, &m);
+  int rc = wbc::model_checked("wbc_ground_create", model, &m);
   if (rc) return rc;
   wbc_ground_params P;
   default_params(m, &P);
@@ -311,7 +311,7 @@ int wbc_ground_create(const wbc_model* model, const wbc_ground_params* params, i
   const bool fin = P.stiffness < INFINITY && P.dissipation < INFINITY && P.mu < INFINITY && P.v_stiction < INFINITY &&
                    fabs(P.foot_radius) < INFINITY && P.max_substep < INFINITY && fabs(P.fall_height) < INFINITY;
   if (!fin || !(P.stiffness > 0) || !(P.dissipation >= 0) || !(P.mu > 0) || !(P.v_stiction > 0) || !(P.tau_max > 0) || !(P.max_substep > 0))
-    return wbc::plant_misuse("wbc_ground_create: stiffness, mu, v_stiction, tau_max and max_substep must be positive, dissipation "
+    return wbc::misuse("wbc_ground_create: stiffness, mu, v_stiction, tau_max and max_substep must be positive, dissipation "
                              "non-negative, and all but tau_max finite");
   wbc::ModelC* d = nullptr;
   rc = wbc::plant_model_upload(device, m, &d);
@@ -342,7 +342,7 @@ int wbc_ground_forward(wbc_ground g, void* hip_stream, int n, int ld, const doub
   const int rc = check_ground_args("wbc_ground_forward", g, n, ld, q, v, tau);
   if (rc) return rc;
   if (n == 0) return 0;
-  WBC_ON_DEVICE(g->device, wbc::plant_fail);
+  WBC_ON_DEVICE(g->device, wbc::fail);
   // the forward kernel never writes q or v
   return launch_ground(g, (hipStream_t)hip_stream, false,
                        make_args(g, n, ld, 1, 0.0, const_cast<double*>(q), const_cast<double*>(v), nullptr, tau, mu, mass_scale,
@@ -357,7 +357,7 @@ int wbc_ground_step(wbc_ground g, void* hip_stream, int n, int ld, double dt, do
   const int sub = substeps_for("wbc_ground_step", g, dt);
   if (sub < 0) return sub;
   if (n == 0) return 0;
-  WBC_ON_DEVICE(g->device, wbc::plant_fail);
+  WBC_ON_DEVICE(g->device, wbc::fail);
   return launch_ground(g, (hipStream_t)hip_stream, true,
                        make_args(g, n, ld, sub, dt, q, v, time, tau, mu, mass_scale, ext_wrench, nullptr, force, contact, flags, counts));
 }
@@ -368,9 +368,9 @@ int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stre
                        double* metrics, int32_t* status, double* force, uint8_t* contact, int32_t* flags, int32_t* counts) {
   const int rc = check_ground_args("wbc_ground_rollout", g, n, ld, q, v, tau);
   if (rc) return rc;
-  if (!h || !traj) return wbc::plant_misuse("wbc_ground_rollout: null controller or trajectory handle");
-  if (steps < 0) return wbc::plant_misuse("wbc_ground_rollout: steps must be >= 0");
-  if (n > 0 && (!time || !targets || !contact_mask)) return wbc::plant_misuse("wbc_ground_rollout: time, targets and contact_mask are required");
+  if (!h || !traj) return wbc::misuse("wbc_ground_rollout: null controller or trajectory handle");
+  if (steps < 0) return wbc::misuse("wbc_ground_rollout: steps must be >= 0");
+  if (n > 0 && (!time || !targets || !contact_mask)) return wbc::misuse("wbc_ground_rollout: time, targets and contact_mask are required");
   const int sub = substeps_for("wbc_ground_rollout", g, dt);
   if (sub < 0) return sub;
   const GroundArgs a = make_args(g, n, ld, sub, dt, q, v, time, tau, ground_mu, ground_mass_scale, ext_wrench, nullptr, force, contact,
@@ -380,25 +380,25 @@ int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stre
 }
 
 int wbc_ground_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
-  if (!g) return wbc::plant_misuse("wbc_ground_kernel_info: null ground handle");
+  if (!g) return wbc::misuse("wbc_ground_kernel_info: null ground handle");
   return WBC_PLANT_KERNEL_INFO(g->device, wbc_ground_step_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
 }
 
 int wbc_terrain_check(const wbc_terrain_profile* profiles, int count) {
   char b[256];
-  if (!profiles) return wbc::plant_misuse("wbc_terrain_check: null profiles");
-  if (count < 1 || count > WBC_GROUND_MAX_PROFILES) return wbc::plant_misuse("wbc_terrain_check: count must be 1 .. WBC_GROUND_MAX_PROFILES (16)");
+  if (!profiles) return wbc::misuse("wbc_terrain_check: null profiles");
+  if (count < 1 || count > WBC_GROUND_MAX_PROFILES) return wbc::misuse("wbc_terrain_check: count must be 1 .. WBC_GROUND_MAX_PROFILES (16)");
   for (int p = 0; p < count; p++) {
     const wbc_terrain_profile& t = profiles[p];
     const char* what = wbc::terrain_profile_error(t.nk, t.x0, t.y0, t.yaw, t.s, t.h);
-    if (what) { snprintf(b, sizeof b, "wbc_terrain_check: profile %d: %s", p, what); return wbc::plant_misuse(b); }
+    if (what) { snprintf(b, sizeof b, "wbc_terrain_check: profile %d: %s", p, what); return wbc::misuse(b); }
   }
   return 0;
 }
 
 int wbc_ground_set_terrain(wbc_ground g, const wbc_terrain_profile* profiles, int count, const uint8_t* terrain_id,
                            const double* terrain_scale) {
-  if (!g) return wbc::plant_misuse("wbc_ground_set_terrain: null ground handle");
+  if (!g) return wbc::misuse("wbc_ground_set_terrain: null ground handle");
   if (!profiles || count == 0) {
     g->terrain = TerrainArgs{};
     return 0;
@@ -411,11 +411,11 @@ int wbc_ground_set_terrain(wbc_ground g, const wbc_terrain_profile* profiles, in
     const wbc_terrain_profile& t = profiles[p];
     wbc::terrain_pack(t.nk, t.x0, t.y0, t.yaw, t.s, t.h, table + p * wbc::TERRAIN_STRIDE);
   }
-  WBC_ON_DEVICE(g->device, wbc::plant_fail);
-  if (!g->d_terrain) WBC_PLANT_TRY(hipMalloc(&g->d_terrain, sizeof table));
-  WBC_PLANT_TRY(hipDeviceSynchronize());   // a launch still reading the previous table
+  WBC_ON_DEVICE(g->device, wbc::fail);
+  if (!g->d_terrain) HIP_TRY(hipMalloc(&g->d_terrain, sizeof table));
+  HIP_TRY(hipDeviceSynchronize());   // a launch still reading the previous table
   g->terrain = TerrainArgs{};
-  WBC_PLANT_TRY(hipMemcpy(g->d_terrain, table, (size_t)count * wbc::TERRAIN_STRIDE * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(g->d_terrain, table, (size_t)count * wbc::TERRAIN_STRIDE * sizeof(double), hipMemcpyHostToDevice));
   g->terrain.table = g->d_terrain;
   g->terrain.id = terrain_id;
   g->terrain.scale = terrain_scale;
@@ -424,7 +424,7 @@ int wbc_ground_set_terrain(wbc_ground g, const wbc_terrain_profile* profiles, in
 }
 
 int wbc_ground_terrain_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
-  if (!g) return wbc::plant_misuse("wbc_ground_terrain_kernel_info: null ground handle");
+  if (!g) return wbc::misuse("wbc_ground_terrain_kernel_info: null ground handle");
   return WBC_PLANT_KERNEL_INFO(g->device, wbc_ground_terrain_step_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
 }
 

@@ -14,6 +14,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/wbc.h"
@@ -26,24 +27,12 @@ __device__ unsigned long long g_wbc_stamps[16 * 4096];
 #include "wbc_hex.hpp"
 #include "wbc_traj_dev.hpp"
 #include "wbc_device_guard.hpp"
+#include "wbc_host.hpp"
+
+using wbc::fail;
+using wbc::misuse;
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(const char* what, hipError_t e) {
-  snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-  return -2;
-}
-int misuse(const char* what) {
-  snprintf(g_err, sizeof g_err, "%s", what);
-  return -1;
-}
-#define HIP_TRY(x)                                  \
-  do {                                              \
-    hipError_t e_ = (x);                            \
-    if (e_ != hipSuccess) return fail(#x, e_);      \
-  } while (0)
 
 struct StatsDev {
   double ticks, status_nonzero, iters_sum, tau_abs_sum;
@@ -52,7 +41,6 @@ struct StatsDev {
   double mask_count[16];
 };
 
-constexpr int BLOCK = 64;
 // The end-of-rollout statistics are accumulated with fire-and-forget atomics into one of STAT_SLOTS
 // per-block slots: 22 atomics per wavefront on ONE address set serialise in L2 (measured: +50 us at
 // 1024 wavefronts, profiles/r02); spread over slots they pipeline.  wbc_stats_get reduces the slots.
@@ -546,7 +534,9 @@ wbc_hex_rollout_kernel(const wbc::ModelC* __restrict__ mp, const wbc::ParamsX* _
       }
     }
     __syncthreads();
-    // ---- forward step, same arithmetic as wbc_integrate_kernel: v+ = v + dt vd; orientation by exp(dt/2 w+); p, joints by v+
+    // ---- forward step, same arithmetic as wbc_integrate_kernel: v+ = v + dt vd; orientation by exp(dt/2 w+); p, joints by v+.
+    // The lead lane's orientation update below must equal wbc::quat_step (wbc_model.hpp) term for term; it stays written out
+    // because the call does not compile to the same instructions here, in kernels that sit at the edge of spilling.
 #pragma unroll
     for (int r = h; r < 18; r += 16) {
       const double vn = inbuf[(19 + r) * HROBOTS + slot] + dt * vdbuf[slot * 18 + r];
@@ -612,21 +602,7 @@ __global__ void __launch_bounds__(64) wbc_integrate_kernel(int n, int ld, double
   for (int r = 0; r < 19; r++) qq[r] = q[(size_t)r * ld + i];
 #pragma unroll
   for (int r = 0; r < 18; r++) vn[r] = vn[r] + dt * vd[(size_t)r * ld + i];
-  // orientation: q+ = exp(dt/2 w) (x) q, w in the world frame
-  const double wn = sqrt(vn[0] * vn[0] + vn[1] * vn[1] + vn[2] * vn[2]);
-  const double ang = 0.5 * wn * dt;
-  double dw = 1.0, dx = 0.0, dy = 0.0, dz = 0.0;
-  if (wn > 0.0) {
-    const double sc = sin(ang) / wn;
-    dw = cos(ang); dx = sc * vn[0]; dy = sc * vn[1]; dz = sc * vn[2];
-  }
-  const double w1 = qq[0], x1 = qq[1], y1 = qq[2], z1 = qq[3];
-  double qw = dw * w1 - dx * x1 - dy * y1 - dz * z1;
-  double qx = dw * x1 + dx * w1 + dy * z1 - dz * y1;
-  double qy = dw * y1 - dx * z1 + dy * w1 + dz * x1;
-  double qz = dw * z1 + dx * y1 - dy * x1 + dz * w1;
-  const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-  qq[0] = qw * inv; qq[1] = qx * inv; qq[2] = qy * inv; qq[3] = qz * inv;
+  wbc::quat_step(dt, vn[0], vn[1], vn[2], qq);   // orientation: q+ = exp(dt/2 w) (x) q, w in the world frame
 #pragma unroll
   for (int r = 0; r < 3; r++) qq[4 + r] += dt * vn[3 + r];
 #pragma unroll
@@ -664,8 +640,7 @@ __global__ void wbc_advance_time_kernel(int n, double dt, double* __restrict__ t
 }  // namespace
 
 struct wbc_handle_s {
-  int kind, max_batch, device, variant;
-  int last_variant;  // kernel used by the most recent launch (1 lane, 2 quad, 3 hex)
+  int kind, max_batch, device;
   bool torque_box;
   uint32_t flags;
   hipStream_t stream;
@@ -708,8 +683,49 @@ static int zc_finish(wbc_handle_s* h) {   // the pending small-batch tick: wait,
 }
 
 extern "C" int wbc_traj_raw_(wbc_traj t, wbc::TrajDev* out);   // wbc_traj.hip (internal)
-// internal: wbc_traj.hip reports its failures through the same thread-local buffer wbc_last_error() returns
+// internal: every translation unit reports its failures (wbc_host.hpp) through the one thread-local buffer wbc_last_error() returns
+static thread_local char g_err[512] = "";
 extern "C" void wbc_set_error_(const char* msg) { snprintf(g_err, sizeof g_err, "%s", msg ? msg : ""); }
+
+// ---------------------------------------------------------------- the tick kernels, [torque box][law]
+// The one place that says which kernel runs a handle's (law, torque box): launch(), wbc_rollout and the two *_kernel_info entry
+// points all go through tick_kernels(), so the registers kernel_info reports are those of the kernel that is launched.
+// torque box: a second constraint slot per lane, |tau_j| <= tau_max (wbc_hex.hpp).  A null entry is not part of this build.
+struct TickKernels {
+  decltype(&wbc_hex_kernel<wbc::KIND_ID, false>) tick;
+  decltype(&wbc_hex_rollout_kernel<wbc::KIND_ID, false>) rollout;
+};
+struct TickTable { TickKernels law[2][4]; };
+static_assert(WBC_KIND_ID == 0 && WBC_KIND_MPTC == 1 && WBC_KIND_PC == 2 && WBC_KIND_CLF == 3, "the table's second index is the ABI's kind");
+static const TickTable kTickKernels = [] {
+  TickTable t{};
+#ifdef WBC_DEV_ONLY   // diagnostic builds (tools/build_cuts.sh): ONE law instantiated, seconds to compile
+  t.law[false][WBC_DEV_ONLY].tick = wbc_hex_kernel<WBC_DEV_ONLY, false>;
+#else
+  // The code object lays the kernels out in the order of their first mention, and placement alone moves the headline by up to 2 %
+  // (DESIGN.md section 8): the order stays what it has been -- ticks before rollouts, torque box before plain.
+  auto ticks = [&t](auto tb) {
+    constexpr bool TB = decltype(tb)::value;
+    t.law[TB][WBC_KIND_ID].tick = wbc_hex_kernel<wbc::KIND_ID, TB>;     t.law[TB][WBC_KIND_MPTC].tick = wbc_hex_kernel<wbc::KIND_MPTC, TB>;
+    t.law[TB][WBC_KIND_PC].tick = wbc_hex_kernel<wbc::KIND_PC, TB>;     t.law[TB][WBC_KIND_CLF].tick = wbc_hex_kernel<wbc::KIND_CLF, TB>;
+  };
+  auto rollouts = [&t](auto tb) {
+    constexpr bool TB = decltype(tb)::value;
+    t.law[TB][WBC_KIND_ID].rollout = wbc_hex_rollout_kernel<wbc::KIND_ID, TB>;   t.law[TB][WBC_KIND_MPTC].rollout = wbc_hex_rollout_kernel<wbc::KIND_MPTC, TB>;
+    t.law[TB][WBC_KIND_PC].rollout = wbc_hex_rollout_kernel<wbc::KIND_PC, TB>;   t.law[TB][WBC_KIND_CLF].rollout = wbc_hex_rollout_kernel<wbc::KIND_CLF, TB>;
+  };
+  ticks(std::true_type{}); ticks(std::false_type{}); rollouts(std::true_type{}); rollouts(std::false_type{});
+#endif
+  return t;
+}();
+
+// the kernels of h's law; `rollout_fn`: the entry point that needs the rollout kernel, or null
+static int tick_kernels(const wbc_handle_s* h, const char* rollout_fn, TickKernels* out) {
+  *out = kTickKernels.law[h->torque_box][h->kind];
+  if (rollout_fn && !out->rollout) return misuse(rollout_fn, "not part of a WBC_DEV_ONLY diagnostic build");
+  if (!out->tick) return misuse("this diagnostic build carries one law only (WBC_DEV_ONLY)");
+  return 0;
+}
 
 extern "C" {
 
@@ -729,21 +745,7 @@ int wbc_create(const wbc_model* model, int kind, const wbc_params* params, int m
   if (kind < WBC_KIND_ID || kind > WBC_KIND_CLF) return misuse("wbc_create: kind must be WBC_KIND_ID, _MPTC, _PC or _CLF");
   if (max_batch <= 0 || max_batch > WBC_MAX_LD) return misuse("wbc_create: max_batch must be in 1 .. WBC_MAX_LD (2^23)");
   wbc::ModelC m;
-  if (wbc::model_from_flat(model->flat, &m)) return misuse("wbc_create: joint axes must be axis-aligned");
-  if (!wbc::model_axes_are_xyy(&m))
-    return misuse("wbc_create: unsupported kinematic tree -- the kernels are specialised to legs with the abduction joint "
-                  "about +-x and the hip and knee joints about +-y (Mini Cheetah, ANYmal)");
-  bool seen_q[12] = {0}, seen_a[12] = {0};
-  for (int i = 0; i < 12; i++) {
-    int a = model->q_perm[i], b = model->act_perm[i];
-    if (a < 0 || a >= 12 || b < 0 || b >= 12 || seen_q[a] || seen_a[b]) return misuse("wbc_create: q_perm/act_perm must be permutations of 0..11");
-    seen_q[a] = seen_a[b] = true;
-  }
-  {
-    int qp[12], ap[12];
-    for (int i = 0; i < 12; i++) { qp[i] = model->q_perm[i]; ap[i] = model->act_perm[i]; }
-    wbc::model_set_perms(&m, qp, ap);
-  }
+  if (const int rc = wbc::model_checked("wbc_create", model, &m)) return rc;
   wbc::ParamsC P;
   wbc::params_default(kind, &P);
   if (params) memcpy(&P, params, sizeof P);
@@ -752,7 +754,6 @@ int wbc_create(const wbc_model* model, int kind, const wbc_params* params, int m
   WBC_ON_DEVICE(device, fail);
   wbc_handle h = new wbc_handle_s();
   h->kind = kind; h->max_batch = max_batch; h->device = device; h->flags = flags;
-  h->variant = 0;
   h->torque_box = P.tau_max < 1e300;
   // every allocation below is released by wbc_destroy on failure (null members are skipped)
   auto build = [&]() -> int {
@@ -830,43 +831,15 @@ int wbc_set_stream(wbc_handle h, void* hip_stream) {
   return 0;
 }
 
-// One product kernel family (16 lanes per robot) for every law, batch size and option; the variant number (3) is
-// kept in the ABI for compatibility with round-1 callers.
-static int pick_variant(const wbc_handle_s*, int) { return 3; }
-
 static int launch(wbc_handle h, int n, int ld, const double* q, const double* v, const double* tg,
                   const uint8_t* mask, const double* mu, const double* ms, double* tau, double* met,
                   int32_t* status) {
-  h->last_variant = 3;
-  StatsDev* d_stats = h->d_stats;
-  dim3 grid((n + HROBOTS - 1) / HROBOTS);
-#ifdef WBC_DEV_ONLY   // diagnostic builds (tools/build_cuts.sh): ONE law instantiated, seconds to compile
-  if (h->kind != WBC_DEV_ONLY || h->torque_box) return misuse("this diagnostic build carries one law only (WBC_DEV_ONLY)");
-  hipLaunchKernelGGL((wbc_hex_kernel<WBC_DEV_ONLY, false>), grid, dim3(HEX_BLOCK), 0, h->stream, h->d_model, h->d_params, n, ld, q, v,
-                     tg, mask, mu, ms, tau, met, status, d_stats, h->d_vdot);
+  TickKernels k;
+  if (const int rc = tick_kernels(h, nullptr, &k)) return rc;
+  hipLaunchKernelGGL(k.tick, dim3((n + HROBOTS - 1) / HROBOTS), dim3(HEX_BLOCK), 0, h->stream, h->d_model, h->d_params, n, ld, q, v, tg,
+                     mask, mu, ms, tau, met, status, h->d_stats, h->d_vdot);
   HIP_TRY(hipGetLastError());
   return 0;
-#else
-#define WBC_HEX_ARGS grid, dim3(HEX_BLOCK), 0, h->stream, h->d_model, h->d_params, n, ld, q, v, tg, mask, mu, ms, tau, met, status, d_stats, h->d_vdot
-  if (h->torque_box) {   // second constraint slot per lane: |tau_j| <= tau_max (wbc_hex.hpp)
-    switch (h->kind) {
-      case WBC_KIND_ID: hipLaunchKernelGGL((wbc_hex_kernel<wbc::KIND_ID, true>), WBC_HEX_ARGS); break;
-      case WBC_KIND_MPTC: hipLaunchKernelGGL((wbc_hex_kernel<wbc::KIND_MPTC, true>), WBC_HEX_ARGS); break;
-      case WBC_KIND_PC: hipLaunchKernelGGL((wbc_hex_kernel<wbc::KIND_PC, true>), WBC_HEX_ARGS); break;
-      default: hipLaunchKernelGGL((wbc_hex_kernel<wbc::KIND_CLF, true>), WBC_HEX_ARGS);
-    }
-  } else {
-    switch (h->kind) {
-      case WBC_KIND_ID: hipLaunchKernelGGL((wbc_hex_kernel<wbc::KIND_ID, false>), WBC_HEX_ARGS); break;
-      case WBC_KIND_MPTC: hipLaunchKernelGGL((wbc_hex_kernel<wbc::KIND_MPTC, false>), WBC_HEX_ARGS); break;
-      case WBC_KIND_PC: hipLaunchKernelGGL((wbc_hex_kernel<wbc::KIND_PC, false>), WBC_HEX_ARGS); break;
-      default: hipLaunchKernelGGL((wbc_hex_kernel<wbc::KIND_CLF, false>), WBC_HEX_ARGS);
-    }
-  }
-#undef WBC_HEX_ARGS
-  HIP_TRY(hipGetLastError());
-  return 0;
-#endif
 }
 
 static int check_step_args(wbc_handle h, int n, int ld, const void* q, const void* v, const void* tg,
@@ -1075,37 +1048,18 @@ int wbc_rollout(wbc_handle h, wbc_traj traj, int steps, double dt, int n, int ld
   if (h->flags & WBC_HOST_PTRS) return misuse("wbc_rollout: needs a WBC_DEVICE_PTRS handle");
   if (steps == 0 || n == 0) return 0;
   WBC_ON_DEVICE(h->device, fail);
-#ifdef WBC_DEV_ONLY
-  return misuse("wbc_rollout: not part of a WBC_DEV_ONLY diagnostic build");
-#else
-  {
-    // the whole rollout is ONE persistent launch per <= 1024 ticks (wbc_hex_rollout_kernel)
-    wbc::TrajDev T;
-    if (wbc_traj_raw_(traj, &T)) return misuse("wbc_rollout: bad trajectory handle");
-    h->last_variant = 3;
-    StatsDev* d_stats = h->d_stats;
-    dim3 grid((n + HROBOTS - 1) / HROBOTS);
-#define WBC_RO_ARGS grid, dim3(HEX_BLOCK), 0, h->stream, h->d_model, h->d_params, n, ld, steps, dt, T, q, v, time, targets, \
-                    contact_mask, mu, mass_scale, tau, metrics, status, d_stats, vdot, (h->warm_start ? 1 : 0)
-#define WBC_RO_KIND(TBV)                                                                                   \
-    switch (h->kind) {                                                                                     \
-      case WBC_KIND_ID: hipLaunchKernelGGL((wbc_hex_rollout_kernel<wbc::KIND_ID, TBV>), WBC_RO_ARGS); break;     \
-      case WBC_KIND_MPTC: hipLaunchKernelGGL((wbc_hex_rollout_kernel<wbc::KIND_MPTC, TBV>), WBC_RO_ARGS); break; \
-      case WBC_KIND_PC: hipLaunchKernelGGL((wbc_hex_rollout_kernel<wbc::KIND_PC, TBV>), WBC_RO_ARGS); break;     \
-      default: hipLaunchKernelGGL((wbc_hex_rollout_kernel<wbc::KIND_CLF, TBV>), WBC_RO_ARGS);                    \
-    }
-    // at most 1024 ticks per launch (~25 ms): long rollouts stay a sequence of bounded kernels
-    const int total = steps;
-    for (int done_steps = 0; done_steps < total; done_steps += 1024) {
-      steps = (total - done_steps < 1024) ? total - done_steps : 1024;
-      if (h->torque_box) { WBC_RO_KIND(true) } else { WBC_RO_KIND(false) }
-    }
-#undef WBC_RO_KIND
-#undef WBC_RO_ARGS
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
-#endif
+  // the whole rollout is ONE persistent launch per <= 1024 ticks (wbc_hex_rollout_kernel, ~25 ms): long rollouts stay a sequence
+  // of bounded kernels
+  TickKernels k;
+  if (const int rc = tick_kernels(h, "wbc_rollout", &k)) return rc;
+  wbc::TrajDev T;
+  if (wbc_traj_raw_(traj, &T)) return misuse("wbc_rollout: bad trajectory handle");
+  for (int done = 0; done < steps; done += 1024)
+    hipLaunchKernelGGL(k.rollout, dim3((n + HROBOTS - 1) / HROBOTS), dim3(HEX_BLOCK), 0, h->stream, h->d_model, h->d_params, n, ld,
+                       (steps - done < 1024) ? steps - done : 1024, dt, T, q, v, time, targets, contact_mask, mu, mass_scale, tau,
+                       metrics, status, h->d_stats, vdot, (h->warm_start ? 1 : 0));
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 int wbc_set_warm_start(wbc_handle h, int on) {
@@ -1114,68 +1068,34 @@ int wbc_set_warm_start(wbc_handle h, int on) {
   return 0;
 }
 
+// One product kernel family (16 lanes per robot) for every law, batch size and option; the variant number (3) is kept in the ABI
+// for compatibility with round-1 callers.
 int wbc_set_variant(wbc_handle h, int variant) {
   if (!h) return misuse("wbc_set_variant: null handle");
   if (variant != 0 && variant != 3)
     return misuse("wbc_set_variant: 0 = auto or 3 = 16 lanes per robot (the lane- and quad-per-robot kernels of round 1 are retired)");
-  h->variant = variant;
   return 0;
 }
 
 int wbc_variant_for(wbc_handle h, int n) {
   if (!h || n < 0) return misuse("wbc_variant_for: bad argument");
-  return pick_variant(h, n);
+  return 3;
 }
 
 int wbc_kernel_info(wbc_handle h, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
   if (!h) return misuse("wbc_kernel_info: null handle");
-  WBC_ON_DEVICE(h->device, fail);
-  hipFuncAttributes a;
-  const void* fn;
-#ifdef WBC_DEV_ONLY
-  fn = (const void*)wbc_hex_kernel<WBC_DEV_ONLY, false>;
-#else
-  if (h->torque_box)
-    fn = h->kind == WBC_KIND_ID ? (const void*)wbc_hex_kernel<wbc::KIND_ID, true>
-       : h->kind == WBC_KIND_MPTC ? (const void*)wbc_hex_kernel<wbc::KIND_MPTC, true>
-       : h->kind == WBC_KIND_PC ? (const void*)wbc_hex_kernel<wbc::KIND_PC, true> : (const void*)wbc_hex_kernel<wbc::KIND_CLF, true>;
-  else
-    fn = h->kind == WBC_KIND_ID ? (const void*)wbc_hex_kernel<wbc::KIND_ID>
-       : h->kind == WBC_KIND_MPTC ? (const void*)wbc_hex_kernel<wbc::KIND_MPTC>
-       : h->kind == WBC_KIND_PC ? (const void*)wbc_hex_kernel<wbc::KIND_PC> : (const void*)wbc_hex_kernel<wbc::KIND_CLF>;
-#endif
-  HIP_TRY(hipFuncGetAttributes(&a, fn));
-  if (num_vgpr) *num_vgpr = a.numRegs;
-  if (scratch_bytes) *scratch_bytes = (int)a.localSizeBytes;
-  if (lds_bytes) *lds_bytes = (int)a.sharedSizeBytes;
-  if (block_threads) *block_threads = HEX_BLOCK;
-  return 0;
+  TickKernels k;
+  if (const int rc = tick_kernels(h, nullptr, &k)) return rc;
+  return wbc::kernel_info(h->device, (const void*)k.tick, "hipFuncGetAttributes(&a, fn)", HEX_BLOCK, num_vgpr, scratch_bytes, lds_bytes,
+                          block_threads);
 }
 
 int wbc_rollout_kernel_info(wbc_handle h, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
   if (!h) return misuse("wbc_rollout_kernel_info: null handle");
-  WBC_ON_DEVICE(h->device, fail);
-  hipFuncAttributes a;
-  const void* fn;
-#ifdef WBC_DEV_ONLY
-  (void)fn; (void)a;
-  return misuse("wbc_rollout_kernel_info: not part of a WBC_DEV_ONLY diagnostic build");
-#else
-  if (h->torque_box)
-    fn = h->kind == WBC_KIND_ID ? (const void*)wbc_hex_rollout_kernel<wbc::KIND_ID, true>
-       : h->kind == WBC_KIND_MPTC ? (const void*)wbc_hex_rollout_kernel<wbc::KIND_MPTC, true>
-       : h->kind == WBC_KIND_PC ? (const void*)wbc_hex_rollout_kernel<wbc::KIND_PC, true> : (const void*)wbc_hex_rollout_kernel<wbc::KIND_CLF, true>;
-  else
-    fn = h->kind == WBC_KIND_ID ? (const void*)wbc_hex_rollout_kernel<wbc::KIND_ID, false>
-       : h->kind == WBC_KIND_MPTC ? (const void*)wbc_hex_rollout_kernel<wbc::KIND_MPTC, false>
-       : h->kind == WBC_KIND_PC ? (const void*)wbc_hex_rollout_kernel<wbc::KIND_PC, false> : (const void*)wbc_hex_rollout_kernel<wbc::KIND_CLF, false>;
-#endif
-  HIP_TRY(hipFuncGetAttributes(&a, fn));
-  if (num_vgpr) *num_vgpr = a.numRegs;
-  if (scratch_bytes) *scratch_bytes = (int)a.localSizeBytes;
-  if (lds_bytes) *lds_bytes = (int)a.sharedSizeBytes;
-  if (block_threads) *block_threads = HEX_BLOCK;
-  return 0;
+  TickKernels k;
+  if (const int rc = tick_kernels(h, "wbc_rollout_kernel_info", &k)) return rc;
+  return wbc::kernel_info(h->device, (const void*)k.rollout, "hipFuncGetAttributes(&a, fn)", HEX_BLOCK, num_vgpr, scratch_bytes,
+                          lds_bytes, block_threads);
 }
 
 }  // extern "C"

@@ -67,4 +67,22 @@ inline void params_default(int kind, ParamsC* p) {
   p->tau_max = INFINITY; p->eps2 = 1e-8;
 }
 
+// The orientation update of every forward step: q4 <- exp(dt/2 w) (x) q4, renormalised; w = (w0, w1, w2) in the world frame.
+template <class T> WBC_HD void quat_step(T dt, T w0, T w1, T w2, T* q4) {
+  const T wn = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+  const T ang = T(0.5) * wn * dt;
+  T dw = T(1.0), dx = T(0.0), dy = T(0.0), dz = T(0.0);
+  if (wn > T(0.0)) {
+    const T sc = sin(ang) / wn;
+    dw = cos(ang); dx = sc * w0; dy = sc * w1; dz = sc * w2;
+  }
+  const T w1q = q4[0], x1 = q4[1], y1 = q4[2], z1 = q4[3];
+  const T qw = dw * w1q - dx * x1 - dy * y1 - dz * z1;
+  const T qx = dw * x1 + dx * w1q + dy * z1 - dz * y1;
+  const T qy = dw * y1 - dx * z1 + dy * w1q + dz * x1;
+  const T qz = dw * z1 + dx * y1 - dy * x1 + dz * w1q;
+  const T inv = T(1.0) / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
+  q4[0] = qw * inv; q4[1] = qx * inv; q4[2] = qy * inv; q4[3] = qz * inv;
+}
+
 }  // namespace wbc

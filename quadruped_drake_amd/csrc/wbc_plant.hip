@@ -235,7 +235,7 @@ int launch_plant(wbc_plant p, hipStream_t s, bool step, const PlantArgs& a) {
     hipLaunchKernelGGL(wbc_plant_step_kernel, grid, block, 0, s, p->d_model, a);
   else
     hipLaunchKernelGGL(wbc_plant_forward_kernel, grid, block, 0, s, p->d_model, a);
-  WBC_PLANT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -253,7 +253,7 @@ PlantArgs make_args(wbc_plant p, int n, int ld, double dt, double* q, double* v,
 extern "C" {
 
 int wbc_plant_params_default(wbc_plant_params* out) {
-  if (!out) return wbc::plant_misuse("wbc_plant_params_default: null argument");
+  if (!out) return wbc::misuse("wbc_plant_params_default: null argument");
   out->Kd_contact = 100.0;
   out->tau_max = INFINITY;
   out->mu = 1.0;
@@ -261,15 +261,15 @@ int wbc_plant_params_default(wbc_plant_params* out) {
 }
 
 int wbc_plant_create(const wbc_model* model, const wbc_plant_params* params, int device, wbc_plant* out) {
-  if (!model || !out) return wbc::plant_misuse("wbc_plant_create: null argument");
+  if (!model || !out) return wbc::misuse("wbc_plant_create: null argument");
   wbc::ModelC m;
-  int rc = wbc::plant_model("wbc_plant_create", model, &m);
+  int rc = wbc::model_checked("wbc_plant_create", model, &m);
   if (rc) return rc;
   wbc_plant_params P;
   wbc_plant_params_default(&P);
   if (params) P = *params;
   if (!(P.mu > 0) || !(P.tau_max > 0) || !(P.Kd_contact >= 0) || P.mu == INFINITY || P.Kd_contact == INFINITY)
-    return wbc::plant_misuse("wbc_plant_create: mu must be positive and finite, tau_max positive, Kd_contact non-negative and finite");
+    return wbc::misuse("wbc_plant_create: mu must be positive and finite, tau_max positive, Kd_contact non-negative and finite");
   wbc::ModelC* d = nullptr;
   rc = wbc::plant_model_upload(device, m, &d);
   if (rc) return rc;
@@ -296,7 +296,7 @@ int wbc_plant_forward(wbc_plant p, void* hip_stream, int n, int ld, const double
   const int rc = check_plant_args("wbc_plant_forward", p, n, ld, q, v, tau, contact_mask);
   if (rc) return rc;
   if (n == 0) return 0;
-  WBC_ON_DEVICE(p->device, wbc::plant_fail);
+  WBC_ON_DEVICE(p->device, wbc::fail);
   // the forward kernel never writes q or v
   return launch_plant(p, (hipStream_t)hip_stream, false,
                       make_args(p, n, ld, 0.0, const_cast<double*>(q), const_cast<double*>(v), nullptr, tau, contact_mask, mu,
@@ -309,7 +309,7 @@ int wbc_plant_step(wbc_plant p, void* hip_stream, int n, int ld, double dt, doub
   const int rc = check_plant_args("wbc_plant_step", p, n, ld, q, v, tau, contact_mask);
   if (rc) return rc;
   if (n == 0) return 0;
-  WBC_ON_DEVICE(p->device, wbc::plant_fail);
+  WBC_ON_DEVICE(p->device, wbc::fail);
   return launch_plant(p, (hipStream_t)hip_stream, true,
                       make_args(p, n, ld, dt, q, v, time, tau, contact_mask, mu, mass_scale, vdot, force, flags, counts));
 }
@@ -320,16 +320,16 @@ int wbc_plant_rollout(wbc_handle h, wbc_plant p, wbc_traj traj, void* hip_stream
                       double* force, int32_t* flags, int32_t* counts) {
   const int rc = check_plant_args("wbc_plant_rollout", p, n, ld, q, v, tau, contact_mask);
   if (rc) return rc;
-  if (!h || !traj) return wbc::plant_misuse("wbc_plant_rollout: null controller or trajectory handle");
-  if (steps < 0) return wbc::plant_misuse("wbc_plant_rollout: steps must be >= 0");
-  if (n > 0 && (!time || !targets)) return wbc::plant_misuse("wbc_plant_rollout: time and targets are required");
+  if (!h || !traj) return wbc::misuse("wbc_plant_rollout: null controller or trajectory handle");
+  if (steps < 0) return wbc::misuse("wbc_plant_rollout: steps must be >= 0");
+  if (n > 0 && (!time || !targets)) return wbc::misuse("wbc_plant_rollout: time and targets are required");
   const PlantArgs a = make_args(p, n, ld, dt, q, v, time, tau, contact_mask, plant_mu, plant_mass_scale, nullptr, force, flags, counts);
   return wbc::plant_rollout("wbc_plant_rollout", h, traj, p->device, hip_stream, steps, n, ld, q, v, time, targets, contact_mask, mu,
                             mass_scale, tau, metrics, status, [&] { return launch_plant(p, (hipStream_t)hip_stream, true, a); });
 }
 
 int wbc_plant_kernel_info(wbc_plant p, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
-  if (!p) return wbc::plant_misuse("wbc_plant_kernel_info: null plant handle");
+  if (!p) return wbc::misuse("wbc_plant_kernel_info: null plant handle");
   return WBC_PLANT_KERNEL_INFO(p->device, wbc_plant_step_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
 }
 

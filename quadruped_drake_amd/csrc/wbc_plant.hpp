@@ -17,6 +17,7 @@
 #pragma once
 #include <math.h>
 #include "wbc_tick.hpp"
+#include "wbc_model.hpp"
 
 #if defined(__HIPCC__)
 #define WBC_PLANT_UNROLL _Pragma("unroll")
@@ -323,20 +324,7 @@ template <class T> WBC_HD void plant_integrate_base(T dt, const T* vdb, T* qb, T
   T vn[6];
   WBC_PLANT_UNROLL
   for (int r = 0; r < 6; r++) vn[r] = vb[r] + dt * vdb[r];
-  const T wn = sqrt(vn[0] * vn[0] + vn[1] * vn[1] + vn[2] * vn[2]);
-  const T ang = T(0.5) * wn * dt;
-  T dw = T(1.0), dx = T(0.0), dy = T(0.0), dz = T(0.0);
-  if (wn > T(0.0)) {
-    const T sc = sin(ang) / wn;
-    dw = cos(ang); dx = sc * vn[0]; dy = sc * vn[1]; dz = sc * vn[2];
-  }
-  const T w1 = qb[0], x1 = qb[1], y1 = qb[2], z1 = qb[3];
-  const T qw = dw * w1 - dx * x1 - dy * y1 - dz * z1;
-  const T qx = dw * x1 + dx * w1 + dy * z1 - dz * y1;
-  const T qy = dw * y1 - dx * z1 + dy * w1 + dz * x1;
-  const T qz = dw * z1 + dx * y1 - dy * x1 + dz * w1;
-  const T inv = T(1.0) / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-  qb[0] = qw * inv; qb[1] = qx * inv; qb[2] = qy * inv; qb[3] = qz * inv;
+  quat_step(dt, vn[0], vn[1], vn[2], qb);
   WBC_PLANT_UNROLL
   for (int r = 0; r < 3; r++) qb[4 + r] += dt * vn[3 + r];
   WBC_PLANT_UNROLL

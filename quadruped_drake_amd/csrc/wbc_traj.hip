@@ -12,20 +12,12 @@
 #include "../../include/wbc_extras.h"
 #include "wbc_traj_dev.hpp"
 #include "wbc_device_guard.hpp"
+#include "wbc_host.hpp"
 
-// the one thread-local message buffer behind wbc_last_error() (defined in wbc_kernels.hip)
-extern "C" void wbc_set_error_(const char* msg);
+using wbc::fail;
+using wbc::misuse;
 
 namespace {
-int tfail(const char* what, hipError_t e) {
-  char b[256];
-  snprintf(b, sizeof b, "%s: %s", what, hipGetErrorString(e));
-  wbc_set_error_(b);
-  return -2;
-}
-int tmisuse(const char* what) { wbc_set_error_(what); return -1; }
-#define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return tfail(#x, e_); } while (0)
-
 // lcm_types/trunklcm/trunk_state_t.py:123-133: hash = rotl1(0xbd03c56c9649d0b6)
 constexpr uint64_t kBase = 0xbd03c56c9649d0b6ull;
 constexpr uint64_t kFingerprint = (kBase << 1) + (kBase >> 63);
@@ -179,10 +171,10 @@ int wbc_robot_state_encode(const wbc_robot_state* in, uint8_t* buf, size_t cap) 
 
 int wbc_robot_states_unpack(int device, void* hip_stream, int n, int ld, const uint8_t* msgs, double* q, double* v,
                             uint8_t* ok) {
-  if (n < 0 || ld < n || (n > 0 && (!msgs || !q || !v))) return tmisuse("wbc_robot_states_unpack: bad argument");
-  if (((uintptr_t)msgs & 3u) != 0) return tmisuse("wbc_robot_states_unpack: msgs must be 4-byte aligned");
+  if (n < 0 || ld < n || (n > 0 && (!msgs || !q || !v))) return misuse("wbc_robot_states_unpack: bad argument");
+  if (((uintptr_t)msgs & 3u) != 0) return misuse("wbc_robot_states_unpack: msgs must be 4-byte aligned");
   if (n == 0) return 0;
-  WBC_ON_DEVICE(device, tfail);
+  WBC_ON_DEVICE(device, fail);
   hipLaunchKernelGGL(robot_states_unpack_kernel, dim3((n + 255) / 256, 37), dim3(256), 0, (hipStream_t)hip_stream, n, ld,
                      reinterpret_cast<const uint32_t*>(msgs), q, v, ok);
   HIP_TRY(hipGetLastError());
@@ -191,20 +183,15 @@ int wbc_robot_states_unpack(int device, void* hip_stream, int n, int ld, const u
 
 int wbc_robot_controls_pack(int device, void* hip_stream, int n, int ld, const double* tau, const int* q_perm,
                             const int* act_perm, uint8_t* msgs) {
-  if (n < 0 || ld < n || (n > 0 && (!tau || !msgs))) return tmisuse("wbc_robot_controls_pack: bad argument");
-  if (((uintptr_t)msgs & 3u) != 0) return tmisuse("wbc_robot_controls_pack: msgs must be 4-byte aligned");
+  if (n < 0 || ld < n || (n > 0 && (!tau || !msgs))) return misuse("wbc_robot_controls_pack: bad argument");
+  if (((uintptr_t)msgs & 3u) != 0) return misuse("wbc_robot_controls_pack: msgs must be 4-byte aligned");
   RsSrc src;
-  bool seen[12] = {false};
-  for (int k = 0; k < 12; k++) {
-    const int j = act_perm ? act_perm[k] : k;                       // canonical joint driven by actuator k
-    if (j < 0 || j >= 12) return tmisuse("wbc_robot_controls_pack: act_perm must be a permutation of 0..11");
-    const int jd = q_perm ? q_perm[j] : j;                          // its index in the plant's joint order
-    if (jd < 0 || jd >= 12 || seen[jd]) return tmisuse("wbc_robot_controls_pack: q_perm / act_perm must be permutations of 0..11");
-    seen[jd] = true;
-    src.k[jd] = k;
-  }
+  int jd[12];
+  const int rc = wbc::actuator_joints("wbc_robot_controls_pack", q_perm, act_perm, jd);
+  if (rc) return rc;
+  for (int k = 0; k < 12; k++) src.k[jd[k]] = k;
   if (n == 0) return 0;
-  WBC_ON_DEVICE(device, tfail);
+  WBC_ON_DEVICE(device, fail);
   hipLaunchKernelGGL(robot_controls_pack_kernel, dim3((n + 255) / 256, kRsWords), dim3(256), 0, (hipStream_t)hip_stream, n, ld,
                      tau, src, reinterpret_cast<uint32_t*>(msgs));
   HIP_TRY(hipGetLastError());
@@ -213,22 +200,15 @@ int wbc_robot_controls_pack(int device, void* hip_stream, int n, int ld, const d
 
 int wbc_pd_step(int device, void* hip_stream, int n, int ld, const double* q, const double* v, const double* q_nom19,
                 double kp, double kd, double u_max, const int* q_perm, const int* act_perm, double* tau) {
-  if (n < 0 || ld < n || (n > 0 && (!q || !v || !tau))) return tmisuse("wbc_pd_step: bad argument");
-  if (!(u_max >= 0.0)) return tmisuse("wbc_pd_step: u_max must be non-negative");
+  if (n < 0 || ld < n || (n > 0 && (!q || !v || !tau))) return misuse("wbc_pd_step: bad argument");
+  if (!(u_max >= 0.0)) return misuse("wbc_pd_step: u_max must be non-negative");
   static const double kNominal[3] = {0.0, -0.8, 1.6};   // basic_controller.py:333-340
   PdArgs a;
-  bool seen[12] = {false};
-  for (int k = 0; k < 12; k++) {
-    const int j = act_perm ? act_perm[k] : k;
-    if (j < 0 || j >= 12) return tmisuse("wbc_pd_step: act_perm must be a permutation of 0..11");
-    const int jd = q_perm ? q_perm[j] : j;
-    if (jd < 0 || jd >= 12 || seen[jd]) return tmisuse("wbc_pd_step: q_perm / act_perm must be permutations of 0..11");
-    seen[jd] = true;
-    a.jd[k] = jd;
-    a.qn[k] = q_nom19 ? q_nom19[7 + jd] : kNominal[jd % 3];
-  }
+  const int rc = wbc::actuator_joints("wbc_pd_step", q_perm, act_perm, a.jd);
+  if (rc) return rc;
+  for (int k = 0; k < 12; k++) a.qn[k] = q_nom19 ? q_nom19[7 + a.jd[k]] : kNominal[a.jd[k] % 3];
   if (n == 0) return 0;
-  WBC_ON_DEVICE(device, tfail);
+  WBC_ON_DEVICE(device, fail);
   hipLaunchKernelGGL(pd_step_kernel, dim3((n + 255) / 256, 12), dim3(256), 0, (hipStream_t)hip_stream, n, ld, q, v, a, kp, kd, u_max, tau);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -254,10 +234,10 @@ int wbc_trunk_state_to_targets(const wbc_trunk_state* s, double* t, uint8_t* con
 int wbc_traj_create(int device, int K, const double* timestamps, const double* targets, const uint8_t* masks,
                     const double* standing_targets54, uint8_t standing_mask, double wait_time, wbc_traj* out) {
   if (!out || K < 0 || (K > 0 && (!timestamps || !targets || !masks)) || !standing_targets54)
-    return tmisuse("wbc_traj_create: bad argument");
+    return misuse("wbc_traj_create: bad argument");
   for (int i = 1; i < K; i++)
-    if (!(timestamps[i] >= timestamps[i - 1])) return tmisuse("wbc_traj_create: timestamps must be non-decreasing");
-  WBC_ON_DEVICE(device, tfail);
+    if (!(timestamps[i] >= timestamps[i - 1])) return misuse("wbc_traj_create: timestamps must be non-decreasing");
+  WBC_ON_DEVICE(device, fail);
   wbc_traj t = new wbc_traj_s();
   memset(t, 0, sizeof *t);
   t->device = device; t->K = K; t->wait_time = wait_time; t->standing_mask = standing_mask;
@@ -292,9 +272,9 @@ int wbc_traj_destroy(wbc_traj t) {
 
 int wbc_traj_lookup(wbc_traj t, void* hip_stream, int n, int ld, const double* time, double* targets,
                     uint8_t* contact_mask) {
-  if (!t || n < 0 || (n > 0 && (ld < n || !time || !targets || !contact_mask))) return tmisuse("wbc_traj_lookup: bad argument");
+  if (!t || n < 0 || (n > 0 && (ld < n || !time || !targets || !contact_mask))) return misuse("wbc_traj_lookup: bad argument");
   if (n == 0) return 0;
-  WBC_ON_DEVICE(t->device, tfail);
+  WBC_ON_DEVICE(t->device, fail);
   wbc::TrajDev T{t->K, t->wait_time, t->d_ts, t->d_table, t->d_masks, t->d_standing, t->standing_mask};
   // 64-thread workgroups: a batch of 4096 robots spreads over 64 compute units instead of 16 (the kernel is a latency chain, not a throughput problem)
   hipLaunchKernelGGL(traj_lookup_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)hip_stream, n, ld, T, time,

@@ -14,8 +14,6 @@ steps (terrain.py).  `closed_loop` takes either plant.
 import ctypes as C
 import math
 
-import numpy as np
-
 from . import _lib
 from .controller import load_model
 
@@ -65,28 +63,10 @@ def _L():
 
 
 def _dev_ptr(a, rows, n, tdt, name, device, optional=False):
-    import torch
-    if a is None:
-        if optional:
-            return None
-        raise ValueError(name + " is required")
-    if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == tdt and a.is_contiguous()):
-        raise ValueError("%s: expected a contiguous CUDA tensor of dtype %s" % (name, tdt))
-    if a.device.index != device:
-        raise ValueError("%s: tensor lives on cuda:%s, the plant on cuda:%d" % (name, a.device.index, device))
-    if tuple(a.shape) != ((rows, n) if rows else (n,)):
-        raise ValueError("%s: expected shape %s, got %s" % (name, (rows, n) if rows else (n,), tuple(a.shape)))
-    return C.c_void_p(a.data_ptr())
+    return _lib.dev_ptr(a, rows, n, tdt, name, device, "the plant", optional)
 
 
-def _wbc_model(table, q_perm, act_perm):
-    m = _lib.WbcModel()
-    flat = np.asarray(table["flat"], dtype=np.float64)
-    assert flat.size == 215
-    m.flat[:] = flat.tolist()
-    m.q_perm[:] = list(range(12)) if q_perm is None else [int(x) for x in q_perm]
-    m.act_perm[:] = [int(x) for x in (table.get("act_perm", range(12)) if act_perm is None else act_perm)]
-    return m
+_wbc_model = _lib.fill_model
 
 
 class _Plant:
@@ -117,9 +97,7 @@ class _Plant:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _kernel_info(self, fn):
-        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        _lib.check(fn(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-        return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
+        return _lib.kernel_info(fn, self._h)
 
 
 class RigidContactPlant(_Plant):

@@ -431,18 +431,10 @@ extern "C" int host_hex_rollout(int kind, const double* flat215, const double* p
       if (rc) return rc;
       its += it1;
       bad_total += (st1 != 0);
-      // v+ = v + dt vd ; quat+ = exp(dt/2 w+) (x) quat, renormalised ; p, joints advance with v+
+      // v+ = v + dt vd ; quat+ = exp(dt/2 w+) (x) quat, renormalised (wbc::quat_step) ; p, joints advance with v+
       double vn[18];
       for (int r = 0; r < 18; r++) { vn[r] = v1[r] + dt * vd1[r]; v1[r] = vn[r]; }
-      const double wn = sqrt(vn[0] * vn[0] + vn[1] * vn[1] + vn[2] * vn[2]);
-      const double ang = 0.5 * wn * dt;
-      double dw = 1.0, dx = 0.0, dy = 0.0, dz = 0.0;
-      if (wn > 0.0) { const double sc = sin(ang) / wn; dw = cos(ang); dx = sc * vn[0]; dy = sc * vn[1]; dz = sc * vn[2]; }
-      const double w1 = q1[0], x1 = q1[1], y1 = q1[2], z1 = q1[3];
-      const double qw = dw * w1 - dx * x1 - dy * y1 - dz * z1, qx = dw * x1 + dx * w1 + dy * z1 - dz * y1;
-      const double qy = dw * y1 - dx * z1 + dy * w1 + dz * x1, qz = dw * z1 + dx * y1 - dy * x1 + dz * w1;
-      const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-      q1[0] = qw * inv; q1[1] = qx * inv; q1[2] = qy * inv; q1[3] = qz * inv;
+      wbc::quat_step(dt, vn[0], vn[1], vn[2], q1);
       for (int r = 0; r < 3; r++) q1[4 + r] += dt * vn[3 + r];
       for (int r = 0; r < 12; r++) q1[7 + r] += dt * vn[6 + r];
     }
