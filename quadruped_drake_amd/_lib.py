@@ -13,19 +13,6 @@ c_i32_p = C.POINTER(C.c_int32)
 KIND_ID, KIND_MPTC, KIND_PC, KIND_CLF = 0, 1, 2, 3
 DEVICE_PTRS, HOST_PTRS = 0, 1
 
-# every symbol include/wbc.h (the controller interface), include/wbc_plant.h and include/wbc_ground.h (the plant steps; prototypes in plant.py) and
-# include/wbc_extras.h (frozen out-of-scope exports) declare
-SYMBOLS = ["wbc_last_error", "wbc_version", "wbc_params_default", "wbc_create", "wbc_destroy", "wbc_set_stream",
-           "wbc_step", "wbc_sync", "wbc_time_steps", "wbc_time_steps_result", "wbc_time_steps_each", "wbc_stats_get", "wbc_stats_reset", "wbc_stats_pack", "wbc_stats_reduce", "wbc_set_variant", "wbc_set_warm_start", "wbc_set_vdot_output", "wbc_integrate", "wbc_rollout",
-           "wbc_kernel_info", "wbc_rollout_kernel_info", "wbc_variant_for", "wbc_trunk_state_decode", "wbc_trunk_state_to_targets", "wbc_traj_create",
-           "wbc_traj_destroy", "wbc_traj_lookup", "wbc_robot_state_decode", "wbc_robot_state_encode",
-           "wbc_robot_states_unpack", "wbc_robot_controls_pack", "wbc_pd_step",
-           "wbc_plant_params_default", "wbc_plant_create", "wbc_plant_destroy", "wbc_plant_forward", "wbc_plant_step", "wbc_plant_rollout",
-           "wbc_plant_kernel_info",
-           "wbc_ground_params_default", "wbc_ground_create", "wbc_ground_destroy", "wbc_ground_forward", "wbc_ground_step",
-           "wbc_ground_rollout", "wbc_ground_kernel_info", "wbc_terrain_check", "wbc_ground_set_terrain", "wbc_ground_terrain_kernel_info"]
-
-
 class WbcModel(C.Structure):
     _fields_ = [("flat", C.c_double * 215), ("q_perm", C.c_int32 * 12), ("act_perm", C.c_int32 * 12)]
 
@@ -54,6 +41,87 @@ class WbcRobotState(C.Structure):
     _fields_ = [("q", C.c_float * 19), ("v", C.c_float * 18), ("tau", C.c_float * 12)]
 
 
+class WbcPlantParams(C.Structure):
+    _fields_ = [("Kd_contact", C.c_double), ("tau_max", C.c_double), ("mu", C.c_double)]
+
+
+class WbcGroundParams(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("stiffness", "dissipation", "mu", "v_stiction", "foot_radius", "tau_max", "max_substep",
+                                          "fall_height")]
+
+
+class WbcTerrainProfile(C.Structure):
+    _fields_ = [("nk", C.c_int), ("x0", C.c_double), ("y0", C.c_double), ("yaw", C.c_double), ("s", C.c_double * 8),
+                ("h", C.c_double * 8)]
+
+
+_P, _I, _D = C.c_void_p, C.c_int, C.c_double
+_IP, _FP, _HP = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_void_p)
+_MODEL, _PARAMS, _STATS = C.POINTER(WbcModel), C.POINTER(WbcParams), C.POINTER(WbcStats)
+_TRUNK, _ROBOT = C.POINTER(WbcTrunkState), C.POINTER(WbcRobotState)
+_PLANTP, _GROUNDP = C.POINTER(WbcPlantParams), C.POINTER(WbcGroundParams)
+
+# name: (restype, argtypes) of every function include/wbc.h (the controller interface), include/wbc_plant.h and include/wbc_ground.h (the
+# plant steps) and include/wbc_extras.h (frozen out-of-scope exports) declare, one position per argument in the header's order
+# (tests/test_abi_cpu.py lays each row beside the header's prototype).  A handle, a stream and a device array are _P.
+PROTOTYPES = {
+    "wbc_last_error": (C.c_char_p, []),
+    "wbc_version": (_I, []),
+    "wbc_params_default": (_I, [_I, _PARAMS]),
+    "wbc_create": (_I, [_MODEL, _I, _PARAMS, _I, _I, C.c_uint32, _HP]),
+    "wbc_destroy": (_I, [_P]),
+    "wbc_set_stream": (_I, [_P, _P]),
+    "wbc_step": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "wbc_sync": (_I, [_P]),
+    "wbc_time_steps": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _FP]),
+    "wbc_time_steps_result": (_I, [_P, _FP]),
+    "wbc_time_steps_each": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _FP]),
+    "wbc_stats_get": (_I, [_P, _STATS]),
+    "wbc_stats_reset": (_I, [_P]),
+    "wbc_stats_pack": (_I, [_P, c_double_p]),
+    "wbc_stats_reduce": (_I, [c_double_p, _I, _STATS]),
+    "wbc_set_vdot_output": (_I, [_P, _P]),
+    "wbc_integrate": (_I, [_P, _I, _I, _D, _P, _P, _P]),
+    "wbc_rollout": (_I, [_P, _P, _I, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "wbc_set_warm_start": (_I, [_P, _I]),
+    "wbc_set_variant": (_I, [_P, _I]),
+    "wbc_variant_for": (_I, [_P, _I]),
+    "wbc_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
+    "wbc_rollout_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
+    "wbc_trunk_state_decode": (_I, [C.c_char_p, C.c_size_t, _TRUNK]),
+    "wbc_trunk_state_to_targets": (_I, [_TRUNK, c_double_p, c_u8_p]),
+    "wbc_traj_create": (_I, [_I, _I, c_double_p, c_double_p, c_u8_p, c_double_p, C.c_uint8, _D, _HP]),
+    "wbc_traj_destroy": (_I, [_P]),
+    "wbc_traj_lookup": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "wbc_robot_state_decode": (_I, [C.c_char_p, C.c_size_t, _ROBOT]),
+    "wbc_robot_state_encode": (_I, [_ROBOT, C.c_char_p, C.c_size_t]),
+    "wbc_robot_states_unpack": (_I, [_I, _P, _I, _I, _P, _P, _P, _P]),
+    "wbc_robot_controls_pack": (_I, [_I, _P, _I, _I, _P, _IP, _IP, _P]),
+    "wbc_pd_step": (_I, [_I, _P, _I, _I, _P, _P, c_double_p, _D, _D, _D, _IP, _IP, _P]),
+    "wbc_plant_params_default": (_I, [_PLANTP]),
+    "wbc_plant_create": (_I, [_MODEL, _PLANTP, _I, _HP]),
+    "wbc_plant_destroy": (_I, [_P]),
+    "wbc_plant_forward": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "wbc_plant_step": (_I, [_P, _P, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "wbc_plant_rollout": (_I, [_P, _P, _P, _P, _I, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "wbc_plant_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
+    "wbc_ground_params_default": (_I, [_MODEL, _GROUNDP]),
+    "wbc_ground_create": (_I, [_MODEL, _GROUNDP, _I, _HP]),
+    "wbc_ground_destroy": (_I, [_P]),
+    "wbc_ground_forward": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "wbc_ground_step": (_I, [_P, _P, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "wbc_ground_rollout": (_I, [_P, _P, _P, _P, _I, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "wbc_ground_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
+    "wbc_terrain_check": (_I, [_P, _I]),
+    "wbc_ground_set_terrain": (_I, [_P, _P, _I, _P, _P]),
+    "wbc_ground_terrain_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
+}
+SYMBOLS = list(PROTOTYPES)
+# what a library may lack: an older kernel build under A/B timing (WBC_HIP_LIB; tools/qt.py --lib) the statistics exchange, any library the terrain
+_MAY_LACK = ("wbc_terrain_check", "wbc_ground_set_terrain", "wbc_ground_terrain_kernel_info") + \
+    (("wbc_stats_pack", "wbc_stats_reduce") if "WBC_HIP_LIB" in os.environ else ())
+
+
 class WbcError(RuntimeError):
     pass
 
@@ -76,48 +144,10 @@ def lib():
         except ImportError:
             pass
         l = C.CDLL(LIB_PATH)
-        l.wbc_last_error.restype = C.c_char_p
-        l.wbc_version.restype = C.c_int
-        l.wbc_params_default.argtypes = [C.c_int, C.POINTER(WbcParams)]
-        l.wbc_create.argtypes = [C.POINTER(WbcModel), C.c_int, C.POINTER(WbcParams), C.c_int, C.c_int, C.c_uint32,
-                                 C.POINTER(C.c_void_p)]
-        l.wbc_destroy.argtypes = [C.c_void_p]
-        l.wbc_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-        step_args = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9
-        l.wbc_step.argtypes = step_args
-        l.wbc_sync.argtypes = [C.c_void_p]
-        l.wbc_time_steps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(C.c_float)]
-        l.wbc_time_steps_result.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        l.wbc_time_steps_each.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(C.c_float)]
-        l.wbc_stats_get.argtypes = [C.c_void_p, C.POINTER(WbcStats)]
-        l.wbc_stats_reset.argtypes = [C.c_void_p]
-        ab_build = "WBC_HIP_LIB" in os.environ and not hasattr(l, "wbc_stats_pack")   # an older kernel build under A/B timing (tools/qt.py --lib)
-        if not ab_build:
-            l.wbc_stats_pack.argtypes = [C.c_void_p, c_double_p]
-            l.wbc_stats_reduce.argtypes = [c_double_p, C.c_int, C.POINTER(WbcStats)]
-        l.wbc_set_variant.argtypes = [C.c_void_p, C.c_int]
-        l.wbc_set_warm_start.argtypes = [C.c_void_p, C.c_int]
-        l.wbc_variant_for.argtypes = [C.c_void_p, C.c_int]
-        l.wbc_set_vdot_output.argtypes = [C.c_void_p, C.c_void_p]
-        l.wbc_integrate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.wbc_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 11
-        l.wbc_kernel_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
-        l.wbc_trunk_state_decode.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(WbcTrunkState)]
-        l.wbc_trunk_state_to_targets.argtypes = [C.POINTER(WbcTrunkState), c_double_p, c_u8_p]
-        l.wbc_traj_create.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, c_u8_p, c_double_p, C.c_uint8, C.c_double,
-                                      C.POINTER(C.c_void_p)]
-        l.wbc_traj_destroy.argtypes = [C.c_void_p]
-        l.wbc_traj_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.wbc_robot_state_decode.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(WbcRobotState)]
-        l.wbc_robot_state_encode.argtypes = [C.POINTER(WbcRobotState), C.c_char_p, C.c_size_t]
-        l.wbc_robot_states_unpack.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.wbc_robot_controls_pack.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                              C.c_void_p]
-        l.wbc_pd_step.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_double_p, C.c_double, C.c_double,
-                                  C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
-        for s in SYMBOLS:
-            if not (ab_build and s in ("wbc_stats_pack", "wbc_stats_reduce")):
-                getattr(l, s)
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            if not (name in _MAY_LACK and not hasattr(l, name)):
+                fn = getattr(l, name)
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = l
     return _lib
 

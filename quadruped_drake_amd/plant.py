@@ -15,51 +15,14 @@ import ctypes as C
 import math
 
 from . import _lib
+from ._lib import WbcGroundParams, WbcPlantParams  # noqa: F401 (the mirrors of wbc_plant_params / wbc_ground_params, under their names here)
 from .controller import load_model
 
 PULL, CONE, CLIP, BAD = 1, 2, 4, 8
 SLIP, FELL = 1, 2   # GroundContactPlant's bits 0 and 1 (CLIP and BAD as above)
 
 
-class WbcPlantParams(C.Structure):
-    _fields_ = [("Kd_contact", C.c_double), ("tau_max", C.c_double), ("mu", C.c_double)]
-
-
-class WbcGroundParams(C.Structure):
-    _fields_ = [(k, C.c_double) for k in ("stiffness", "dissipation", "mu", "v_stiction", "foot_radius", "tau_max", "max_substep",
-                                          "fall_height")]
-
-
-_bound = None
-
-
-def _L():
-    """libwbc_hip.so with the prototypes of include/wbc_plant.h"""
-    global _bound
-    if _bound is None:
-        l = _lib.lib()
-        P = C.c_void_p
-        l.wbc_plant_params_default.argtypes = [C.POINTER(WbcPlantParams)]
-        l.wbc_plant_create.argtypes = [C.POINTER(_lib.WbcModel), C.POINTER(WbcPlantParams), C.c_int, C.POINTER(C.c_void_p)]
-        l.wbc_plant_destroy.argtypes = [P]
-        l.wbc_plant_forward.argtypes = [P, P, C.c_int, C.c_int] + [P] * 9
-        l.wbc_plant_step.argtypes = [P, P, C.c_int, C.c_int, C.c_double] + [P] * 11
-        l.wbc_plant_rollout.argtypes = [P, P, P, P, C.c_int, C.c_double, C.c_int, C.c_int] + [P] * 15
-        l.wbc_plant_kernel_info.argtypes = [P] + [C.POINTER(C.c_int)] * 4
-        G = C.POINTER(WbcGroundParams)
-        l.wbc_ground_params_default.argtypes = [C.POINTER(_lib.WbcModel), G]
-        l.wbc_ground_create.argtypes = [C.POINTER(_lib.WbcModel), G, C.c_int, C.POINTER(C.c_void_p)]
-        l.wbc_ground_destroy.argtypes = [P]
-        l.wbc_ground_forward.argtypes = [P, P, C.c_int, C.c_int] + [P] * 10
-        l.wbc_ground_step.argtypes = [P, P, C.c_int, C.c_int, C.c_double] + [P] * 11
-        l.wbc_ground_rollout.argtypes = [P, P, P, P, C.c_int, C.c_double, C.c_int, C.c_int] + [P] * 17
-        l.wbc_ground_kernel_info.argtypes = [P] + [C.POINTER(C.c_int)] * 4
-        if hasattr(l, "wbc_terrain_check"):   # absent from an older kernel build under A/B timing (WBC_HIP_LIB)
-            l.wbc_terrain_check.argtypes = [P, C.c_int]
-            l.wbc_ground_set_terrain.argtypes = [P, P, C.c_int, P, P]
-            l.wbc_ground_terrain_kernel_info.argtypes = [P] + [C.POINTER(C.c_int)] * 4
-        _bound = l
-    return _bound
+_L = _lib.lib   # libwbc_hip.so, bound (the prototypes of every header: _lib.PROTOTYPES)
 
 
 def _dev_ptr(a, rows, n, tdt, name, device, optional=False):

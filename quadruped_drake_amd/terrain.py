@@ -7,19 +7,14 @@ steep segment.  The constructors mirror the terrains the reference ships for its
 towr/include/towr/terrain/examples/height_map_examples.h); the numbers are this project's own.  `GroundContactPlant.set_terrain`
 takes a list of up to 16 profiles; each instance picks one by `terrain_id` and scales it by `terrain_scale`.
 """
-import ctypes as C
 import math
 
 import numpy as np
 
+from ._lib import WbcTerrainProfile   # wbc_terrain_profile of include/wbc_ground.h
+
 MAX_KNOTS = 8
 MAX_PROFILES = 16
-
-
-class WbcTerrainProfile(C.Structure):
-    """wbc_terrain_profile of include/wbc_ground.h"""
-    _fields_ = [("nk", C.c_int), ("x0", C.c_double), ("y0", C.c_double), ("yaw", C.c_double), ("s", C.c_double * MAX_KNOTS),
-                ("h", C.c_double * MAX_KNOTS)]
 
 
 class Profile:

@@ -11,19 +11,49 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = None
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
+_mp = C.POINTER(C.c_ubyte)
+_V, _I, _D = C.c_void_p, C.c_int, C.c_double
+# kind, flat215, params12, q_perm, act_perm, n, stride, q, v, tg, mask, mu, mass_scale, tau, met, status, iters
+_TICK = [_I, _dp, _dp, _ip, _ip, _I, _I, _dp, _dp, _dp, _mp, _dp, _dp, _dp, _dp, _ip, _ip]
+# name: (restype, argtypes), after tools/host_tick.cpp
+_PROTOTYPES = {
+    "host_tick_batch": (_I, _TICK),
+    "host_tick_count": (_I, [_I, _dp, _dp, _I, _I, _dp, _dp, _dp, _mp, _dp, _dp, _dp]),
+    "host_set_vdot_sink": (None, [_V]),
+    "host_hex_batch": (_I, _TICK),
+    "host_gi_dump": (None, [_V]),
+    "host_gi_adds": (None, [_V]),
+    "host_gi_force_bail": (None, [_I]),
+    "host_gi_stats": (None, [_ip, _I]),
+    "host_hex_rollout": (_I, [_I, _dp, _dp, _I, _I, _I, _D, _I, _dp, _dp, _dp, _mp, _dp, _dp, _dp, _dp, _ip, _dp, _ip]),
+    "host_traj_index": (_I, [_dp, _I, _D, _D, _I]),
+}
+
+
+def bind(path):
+    """The library at `path` with the prototypes above; a -DHOST_TICK_HEX_ONLY build (build_variant) exports the hex half of them only."""
+    l = C.CDLL(path)
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        if hasattr(l, name):
+            fn = getattr(l, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    return l
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        _LIB = C.CDLL(graft.build_target("host_tick"))
+        _LIB = bind(graft.build_target("host_tick"))
     return _LIB
+
+
+_default = lib
 
 
 def build_variant(tmp_path, name, flags, compiler=None):
     """A host instantiation of the kernel headers with the CLOSED alternatives available again (the -DWBC_... switches that round 6 removed from
     the product source: tools/lab/patches/closed_switches.patch re-introduces them): the sources are copied to `tmp_path`, patched there and
-    compiled with `flags`.  Without flags the patched tree is the product's code, so a comparison against the default build is a comparison
+    compiled with `flags` and -DHOST_TICK_HEX_ONLY.  Without flags the patched tree is the product's code, so a comparison against the default build is a comparison
     against what ships.  Returns the loaded library."""
     import shutil
     tree = os.path.join(str(tmp_path), "tree_" + name)
@@ -39,7 +69,7 @@ def build_variant(tmp_path, name, flags, compiler=None):
     so = os.path.join(str(tmp_path), name)
     # HOST_TICK_HEX_ONLY: the 16-lane emulation alone (host_hex_batch is all a variant is asked) -- half the compile time of the full tool
     graft.host_shared(so, [os.path.join(tree, "tools", "host_tick.cpp")], ["-pthread", "-DHOST_TICK_HEX_ONLY"] + list(flags), compiler)
-    return C.CDLL(so)
+    return bind(so)
 
 
 def _p(a):
@@ -47,7 +77,9 @@ def _p(a):
 
 
 def run(kind, flat, q, v, targets, mask, mu=None, mass_scale=None, params12=None, q_perm=None, act_perm=None,
-        want_vdot=False, hexv=False):
+        want_vdot=False, hexv=False, lib=None):
+    """One batch through host_tick_batch (hexv: host_hex_batch) of `lib` (None: the default build) -> tau, met, status, iters[, vdot]"""
+    L = _default() if lib is None else lib
     q, v, targets = (np.ascontiguousarray(a, dtype=np.float64) for a in (q, v, targets))
     mask = np.ascontiguousarray(mask, dtype=np.uint8)
     flat = np.ascontiguousarray(flat, dtype=np.float64)
@@ -60,18 +92,18 @@ def run(kind, flat, q, v, targets, mask, mu=None, mass_scale=None, params12=None
     ap = None if act_perm is None else np.ascontiguousarray(act_perm, dtype=np.int32)
     k = {"id": 0, "mptc": 1, "pc": 2, "clf": 3}[kind.lower()] if isinstance(kind, str) else int(kind)
     vdot = np.zeros((18, n)) if want_vdot else None
-    lib().host_set_vdot_sink.argtypes = [C.c_void_p]
-    lib().host_set_vdot_sink(vdot.ctypes.data_as(C.c_void_p) if want_vdot else None)
-    fn = lib().host_hex_batch if hexv else lib().host_tick_batch
-    rc = fn(k, _p(flat), _p(pp), qp.ctypes.data_as(_ip) if qp is not None else None,
-                               ap.ctypes.data_as(_ip) if ap is not None else None, n, n, _p(q), _p(v),
-                               _p(targets), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), _p(mu), _p(ms),
-                               _p(tau), _p(met), st.ctypes.data_as(_ip), it.ctypes.data_as(_ip))
+    if want_vdot:                                    # (a HEX_ONLY variant has no sink)
+        L.host_set_vdot_sink(vdot.ctypes.data_as(C.c_void_p))
+    fn = L.host_hex_batch if hexv else L.host_tick_batch
+    try:
+        rc = fn(k, _p(flat), _p(pp), qp.ctypes.data_as(_ip) if qp is not None else None, ap.ctypes.data_as(_ip) if ap is not None else None,
+                n, n, _p(q), _p(v), _p(targets), mask.ctypes.data_as(_mp), _p(mu), _p(ms), _p(tau), _p(met), st.ctypes.data_as(_ip),
+                it.ctypes.data_as(_ip))
+    finally:
+        if want_vdot:
+            L.host_set_vdot_sink(None)
     assert rc == 0
-    lib().host_set_vdot_sink(None)
-    if want_vdot:
-        return tau, met, st, it, vdot
-    return tau, met, st, it
+    return (tau, met, st, it, vdot) if want_vdot else (tau, met, st, it)
 
 
 def count(kind, flat, q, v, targets, mask, mu=None, mass_scale=None):
@@ -84,6 +116,6 @@ def count(kind, flat, q, v, targets, mask, mu=None, mass_scale=None):
     ms = None if mass_scale is None else np.ascontiguousarray(mass_scale, dtype=np.float64)
     k = {"id": 0, "mptc": 1, "pc": 2, "clf": 3}[kind.lower()] if isinstance(kind, str) else int(kind)
     rc = lib().host_tick_count(k, _p(flat), None, n, n, _p(q), _p(v), _p(targets),
-                               mask.ctypes.data_as(C.POINTER(C.c_ubyte)), _p(mu), _p(ms), _p(out))
+                               mask.ctypes.data_as(_mp), _p(mu), _p(ms), _p(out))
     assert rc == 0
     return dict(zip(["add", "mul", "div", "sqrt", "trig", "cmp"], out))

@@ -24,6 +24,91 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert l.wbc_version() >= 100
 
 
+_MIRRORS = {"wbc_model": "WbcModel", "wbc_params": "WbcParams", "wbc_stats": "WbcStats", "wbc_trunk_state": "WbcTrunkState",
+            "wbc_robot_state": "WbcRobotState", "wbc_plant_params": "WbcPlantParams", "wbc_ground_params": "WbcGroundParams",
+            "wbc_terrain_profile": "WbcTerrainProfile"}
+_BY_VALUE = {"int": C.c_int, "double": C.c_double, "uint32_t": C.c_uint32, "uint8_t": C.c_uint8, "size_t": C.c_size_t}
+_POINTEE = {"double": C.c_double, "int": C.c_int, "int32_t": C.c_int32, "uint8_t": C.c_uint8}
+_HANDLES = ("wbc_handle", "wbc_traj", "wbc_plant", "wbc_ground")
+
+
+def _header_prototypes():
+    """{name: (return type, [argument types])} of every `ret name(args);` in include/*.h, types as written without const and the name"""
+    import glob
+    protos = {}
+    for f in sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))):
+        text = re.sub(r"/\*.*?\*/", "", open(f).read(), flags=re.S)
+        text = re.sub(r"typedef struct \{[^}]*\}[^;]*;", "", text)
+        for ret, name, args in re.findall(r"^((?:const )?\w+\s*\**)\s*(wbc_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+            types = []
+            for a in ([] if args.strip() == "void" else args.split(",")):
+                m = re.match(r"^(?:const )?(\w+)\s*(\**)\s*\w+$", " ".join(a.split()))
+                assert m, (name, a)
+                types.append(m.group(1) + m.group(2))
+            assert name not in protos, name
+            protos[name] = (" ".join(ret.replace("const ", "").split()).replace(" *", "*"), types)
+    return protos
+
+
+def _prototype_mismatches(header, table, lib_mod):
+    """Every disagreement between the headers' prototypes and a prototype table, as "function: what" strings"""
+    bad = ["%s: declared in the headers, missing from the table" % n for n in header if n not in table]
+    bad += ["%s: in the table, not declared in any header" % n for n in table if n not in header]
+    for name in sorted(set(header) & set(table)):
+        (hret, hargs), (restype, argtypes) = header[name], table[name]
+        if restype is not {"int": C.c_int, "char*": C.c_char_p}.get(hret):
+            bad.append("%s: returns %s, the table says %s" % (name, hret, restype))
+        if len(hargs) != len(argtypes):
+            bad.append("%s: %d arguments in the header, %d in the table" % (name, len(hargs), len(argtypes)))
+            continue
+        for i, (h, t) in enumerate(zip(hargs, argtypes)):
+            base = h[:-1]
+            typed = t not in (C.c_void_p, C.c_char_p) and issubclass(t, C._Pointer) and t._type_     # the X of a POINTER(X)
+            if h in _BY_VALUE:
+                ok = t is _BY_VALUE[h]
+            elif not (h.endswith("*") or h in _HANDLES):
+                ok = False                                # a type this check does not know
+            elif base == "float":
+                ok = typed is C.c_float
+            elif base in _MIRRORS:
+                ok = t is C.c_void_p or typed is getattr(lib_mod, _MIRRORS[base])
+            elif typed and base in _POINTEE:              # (so int* meets POINTER(c_int) or c_void_p, never POINTER(c_double))
+                ok = typed is _POINTEE[base]
+            else:
+                ok = t is C.c_void_p or bool(typed) or (t is C.c_char_p and base in ("uint8_t", "char"))
+            if not ok:
+                bad.append("%s: argument %d is %s in the header, %s in the table" % (name, i, h, t))
+    return bad
+
+
+def test_prototype_table_equals_the_headers():
+    """_lib.PROTOTYPES, from which lib() binds every entry point, against the prototypes of include/*.h: the same functions, and per function
+    the return type, the number of arguments and, position by position, the by-value type, pointer-ness and the struct a typed pointer
+    points to.  An argument list that is one pointer short or has two positions swapped does not fail on the CPU -- it is a wrong device
+    pointer inside a kernel -- so it must not get as far as a GPU.  Needs neither the built library nor a GPU.  The checker is then shown
+    three doctored tables and must name the function in each."""
+    from quadruped_drake_amd import _lib
+    header = _header_prototypes()
+    assert len(header) == 50 and header["wbc_last_error"] == ("char*", []) and header["wbc_integrate"][1][3] == "double"
+    assert _prototype_mismatches(header, _lib.PROTOTYPES, _lib) == []
+    assert _lib.SYMBOLS == list(_lib.PROTOTYPES)
+    t = dict(_lib.PROTOTYPES)
+    res, args = t["wbc_ground_rollout"]
+    t["wbc_ground_rollout"] = (res, args[:-1])                                        # one pointer dropped
+    bad = _prototype_mismatches(header, t, _lib)
+    assert len(bad) == 1 and bad[0].startswith("wbc_ground_rollout: 25 arguments in the header, 24"), bad
+    t = dict(_lib.PROTOTYPES)
+    res, args = t["wbc_integrate"]
+    assert (header["wbc_integrate"][1][2:4], args[2:4]) == (["int", "double"], [C.c_int, C.c_double])
+    t["wbc_integrate"] = (res, args[:2] + [args[3], args[2]] + args[4:])              # dt and ld swapped
+    bad = _prototype_mismatches(header, t, _lib)
+    assert len(bad) == 2 and all(b.startswith("wbc_integrate: argument") for b in bad), bad
+    t = dict(_lib.PROTOTYPES)
+    del t["wbc_plant_step"]                                                           # one function missing
+    bad = _prototype_mismatches(header, t, _lib)
+    assert bad == ["wbc_plant_step: declared in the headers, missing from the table"], bad
+
+
 def test_the_boundary_header_is_the_controller_interface_only():
     """include/wbc.h = the reference's controller interface (+ the widened rows of SURVEY 8f); the frozen out-of-scope exports
     (PD law, robot-side wire format) live in include/wbc_extras.h."""
@@ -160,20 +245,19 @@ def test_dpp_hazard_lint_flags_a_violation_and_passes_clean_code(tmp_path):
 
 
 def test_headers_compile_as_c99_and_struct_layouts_equal_the_ctypes_mirrors(tmp_path):
-    """include/wbc.h and include/wbc_extras.h are C headers (`gcc -std=c99 -Wall -pedantic`), and every struct the ctypes
+    """include/wbc.h, wbc_extras.h, wbc_plant.h and wbc_ground.h are C headers (`gcc -std=c99 -Wall -pedantic`), and every struct the ctypes
     mirror in quadruped_drake_amd/_lib.py re-declares by hand has the same size and the same offset for every field: a member
     added on one side only would otherwise be a silent mis-read across the boundary."""
     import subprocess
     from quadruped_drake_amd import _lib
-    mirrors = {"wbc_model": _lib.WbcModel, "wbc_params": _lib.WbcParams, "wbc_stats": _lib.WbcStats,
-               "wbc_trunk_state": _lib.WbcTrunkState, "wbc_robot_state": _lib.WbcRobotState}
+    mirrors = {c: getattr(_lib, m) for c, m in _MIRRORS.items()}
     lines = []
     for cname, cls in mirrors.items():
         lines.append('printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname))
         for f, _ in cls._fields_:
             lines.append('printf("%s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (cname, f, cname, f, cname, f))
     src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "wbc.h"\n#include "wbc_extras.h"\n'
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "wbc.h"\n#include "wbc_extras.h"\n#include "wbc_plant.h"\n#include "wbc_ground.h"\n'
                    'int main(void) {\n  printf("NSTAT %d\\n", WBC_NSTAT);\n  ' + "\n  ".join(lines) + "\n  return 0;\n}\n")
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)],
@@ -193,7 +277,7 @@ def test_headers_compile_as_c99_and_struct_layouts_equal_the_ctypes_mirrors(tmp_
             assert (int(w[2]), int(w[3])) == (fld.offset, fld.size), ln
             seen[w[0]].add(w[1])
     # ... and the other way round: every member the C struct declares is mirrored (member names parsed from the headers)
-    hdr = open(os.path.join(ROOT, "include", "wbc.h")).read() + open(os.path.join(ROOT, "include", "wbc_extras.h")).read()
+    hdr = "".join(open(os.path.join(ROOT, "include", f)).read() for f in ("wbc.h", "wbc_extras.h", "wbc_plant.h", "wbc_ground.h"))
     for cname, cls in mirrors.items():
         body = re.search(r"typedef struct \{([^}]*)\}\s*%s;" % cname, hdr).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)

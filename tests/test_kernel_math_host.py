@@ -253,27 +253,14 @@ def test_evaluation_after_a_drop_and_graded_pivots_on_host(tmp_path):
     order of the QR factor (-DWBC_NATURAL_PIVOTS).  On 4-contact stands (768 of them, the seeds of the round's analysis) the default
     build is within 2e-7 of the oracle compiled in extended precision; a build without either repair is 10x further off on its worst
     robot.  On a trot batch the evaluation never runs (two feet down: one internal-force direction): same bits with and without it."""
-    import ctypes as C
-    import os
-    import subprocess
     from oracle import oracle_ld as old
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dp = C.POINTER(C.c_double)
 
     def build(flags, name):
         return ht.build_variant(tmp_path, name, flags)
 
     def run(L, kind, b):
-        n = b["q"].shape[1]
-        t = orc.load_model_json(b["model"])
-        q, v, tg = (np.ascontiguousarray(b[x]) for x in ("q", "v", "targets"))
-        flat = np.ascontiguousarray(t["flat"], dtype=np.float64)
-        tau = np.zeros((12, n)); met = np.zeros((4, n)); st = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
-        rc = L.host_hex_batch({"id": 0, "mptc": 1}[kind], flat.ctypes.data_as(dp), None, None, None, n, n, q.ctypes.data_as(dp),
-                              v.ctypes.data_as(dp), tg.ctypes.data_as(dp), b["mask"].ctypes.data_as(C.POINTER(C.c_ubyte)), None, None,
-                              tau.ctypes.data_as(dp), met.ctypes.data_as(dp), st.ctypes.data_as(C.POINTER(C.c_int)),
-                              it.ctypes.data_as(C.POINTER(C.c_int)))
-        assert rc == 0 and (st == 0).all()
+        tau, _, st, _ = ht.run(kind, orc.load_model_json(b["model"])["flat"], b["q"], b["v"], b["targets"], b["mask"], hexv=True, lib=L)
+        assert (st == 0).all()
         return tau
 
     from concurrent.futures import ThreadPoolExecutor
@@ -299,25 +286,13 @@ def test_swing_row_compaction_changes_no_bit(tmp_path):
     moved up into the first two block slots, csrc/wbc_hex.hpp) instead of 30 with zero rows.  Blocks move by multiples of three rows, so every
     term keeps its accumulator and its place in the order of the sums: against a build without the compaction
     (-DWBC_NO_SWING_COMPACT) every contact mask gives the same bits."""
-    import ctypes as C
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     L = ht.build_variant(tmp_path, "libhost_tick_nocompact.so", ["-DWBC_NO_SWING_COMPACT"])
-    dp = C.POINTER(C.c_double)
     n = 64
     b = workloads.make_batch(3, n=n)
     t = orc.load_model_json(b["model"])
     mk = (np.arange(n) % 16).astype(np.uint8)          # every contact mask, swing counts 0..4
-    q, v, tg = (np.ascontiguousarray(b[x]) for x in ("q", "v", "targets"))
-    flat = np.ascontiguousarray(t["flat"], dtype=np.float64)
-    for kind, k in (("mptc", 1), ("pc", 2)):
-        tau = np.zeros((12, n)); met = np.zeros((4, n)); st = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
-        rc = L.host_hex_batch(k, flat.ctypes.data_as(dp), None, None, None, n, n, q.ctypes.data_as(dp), v.ctypes.data_as(dp),
-                              tg.ctypes.data_as(dp), mk.ctypes.data_as(C.POINTER(C.c_ubyte)), None, None,
-                              tau.ctypes.data_as(dp), met.ctypes.data_as(dp), st.ctypes.data_as(C.POINTER(C.c_int)),
-                              it.ctypes.data_as(C.POINTER(C.c_int)))
-        assert rc == 0
+    for kind in ("mptc", "pc"):
+        tau, met, st, it = ht.run(kind, t["flat"], b["q"], b["v"], b["targets"], mk, hexv=True, lib=L)
         tau_c, met_c, st_c, it_c = ht.run(kind, t["flat"], b["q"], b["v"], b["targets"], mk, hexv=True)
         assert (st == 0).all() and (st_c == 0).all() and np.array_equal(it, it_c)
         assert np.array_equal(tau_c, tau) and np.array_equal(met_c, met)
@@ -356,24 +331,11 @@ def test_apex_rule_and_deterministic_pick_on_host(tmp_path):
     the tie went either way.  Now a row whose three leg-mates are active is no candidate and the pick quantises its keys (lower index wins a
     tie).  Against a build without either (-DWBC_NO_APEX_RULE -DWBC_PICK_BITS=5): the same solutions, fewer trips on the saturated stands of
     BASELINE config 2, never more than a handful more on any robot; the trot batch keeps its solutions too."""
-    import ctypes as C
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dp = C.POINTER(C.c_double)
     old = ht.build_variant(tmp_path, "libhost_noapex.so", ["-DWBC_NO_APEX_RULE", "-DWBC_PICK_BITS=5"])
 
     def run_old(kind, b):
-        n = b["q"].shape[1]
-        t = orc.load_model_json(b["model"])
-        q, v, tg = (np.ascontiguousarray(b[x]) for x in ("q", "v", "targets"))
-        flat = np.ascontiguousarray(t["flat"], dtype=np.float64)
-        tau = np.zeros((12, n)); met = np.zeros((4, n)); st = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
-        rc = old.host_hex_batch({"id": 0, "mptc": 1}[kind], flat.ctypes.data_as(dp), None, None, None, n, n, q.ctypes.data_as(dp),
-                                v.ctypes.data_as(dp), tg.ctypes.data_as(dp), b["mask"].ctypes.data_as(C.POINTER(C.c_ubyte)), None, None,
-                                tau.ctypes.data_as(dp), met.ctypes.data_as(dp), st.ctypes.data_as(C.POINTER(C.c_int)),
-                                it.ctypes.data_as(C.POINTER(C.c_int)))
-        assert rc == 0 and (st == 0).all()
+        tau, _, st, it = ht.run(kind, orc.load_model_json(b["model"])["flat"], b["q"], b["v"], b["targets"], b["mask"], hexv=True, lib=old)
+        assert (st == 0).all()
         return tau, it
 
     b = workloads.make_batch(2, n=512)
@@ -393,24 +355,10 @@ def test_pick_rule_by_contact_count_on_the_dense_row_laws(tmp_path):
     """Round 5 (csrc/wbc_hex.hpp: hex_gi, HYB; profiles/r05/hybrid_pick.md).  PC and CLF choose the row to add per robot: greatest dual gain with one
     or two feet down, the most violated row with three or four.  Against a build without it (-DWBC_HYBRID_PICK=0: most violated everywhere): the same
     solutions, fewer trips and fewer drops on the trot batch, bit-identical outputs on the 4-contact stands (every robot there is `deep`)."""
-    import ctypes as C
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dp = C.POINTER(C.c_double)
     old = ht.build_variant(tmp_path, "libhost_nohybrid.so", ["-DWBC_HYBRID_PICK=0"])
 
     def run_old(kind, b):
-        n = b["q"].shape[1]
-        t = orc.load_model_json(b["model"])
-        q, v, tg = (np.ascontiguousarray(b[x]) for x in ("q", "v", "targets"))
-        flat = np.ascontiguousarray(t["flat"], dtype=np.float64)
-        tau = np.zeros((12, n)); met = np.zeros((4, n)); st = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
-        rc = old.host_hex_batch({"pc": 2, "clf": 3}[kind], flat.ctypes.data_as(dp), None, None, None, n, n, q.ctypes.data_as(dp),
-                                v.ctypes.data_as(dp), tg.ctypes.data_as(dp), b["mask"].ctypes.data_as(C.POINTER(C.c_ubyte)), None, None,
-                                tau.ctypes.data_as(dp), met.ctypes.data_as(dp), st.ctypes.data_as(C.POINTER(C.c_int)),
-                                it.ctypes.data_as(C.POINTER(C.c_int)))
-        assert rc == 0
+        tau, _, st, it = ht.run(kind, orc.load_model_json(b["model"])["flat"], b["q"], b["v"], b["targets"], b["mask"], hexv=True, lib=old)
         return tau, st, it
 
     for kind in ("pc", "clf"):
@@ -432,23 +380,10 @@ def test_clf_row_built_lazily(tmp_path):
     only in a trip that adds it, instead of reflecting the image through every trip.  Against a build that reflects it (-DWBC_LAZY_DENSE=0): bit-identical
     where the row never binds (the BASELINE batches), the same solution to 1e-10 where it does (body targets pushed 20 x further out: the walk of a few
     robots adds the row), and both within 1e-7 of the oracle."""
-    import ctypes as C
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dp = C.POINTER(C.c_double)
     old = ht.build_variant(tmp_path, "libhost_nolazy.so", ["-DWBC_LAZY_DENSE=0"])
 
     def run_old(b, tg):
-        n = b["q"].shape[1]
-        t = orc.load_model_json(b["model"])
-        q, v, tg = (np.ascontiguousarray(x) for x in (b["q"], b["v"], tg))
-        flat = np.ascontiguousarray(t["flat"], dtype=np.float64)
-        tau = np.zeros((12, n)); met = np.zeros((4, n)); st = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
-        rc = old.host_hex_batch(3, flat.ctypes.data_as(dp), None, None, None, n, n, q.ctypes.data_as(dp), v.ctypes.data_as(dp), tg.ctypes.data_as(dp),
-                                b["mask"].ctypes.data_as(C.POINTER(C.c_ubyte)), None, None, tau.ctypes.data_as(dp), met.ctypes.data_as(dp),
-                                st.ctypes.data_as(C.POINTER(C.c_int)), it.ctypes.data_as(C.POINTER(C.c_int)))
-        assert rc == 0
+        tau, _, st, it = ht.run("clf", orc.load_model_json(b["model"])["flat"], b["q"], b["v"], tg, b["mask"], hexv=True, lib=old)
         return tau, st, it
 
     b = workloads.make_batch(3, n=64)
@@ -474,7 +409,6 @@ def test_no_unwritten_storage_feeds_the_arithmetic(tmp_path):
     and once with every automatic variable pre-filled with the 0xFF..FF pattern (a NaN for a double), must give the same bits on the drop-heavy
     stands and on the trots of every law, with and without the torque box: no value that was never written reaches an instruction that computes.
     (Both builds by the same compiler: gcc and clang round a handful of unannotated expressions differently, 1e-10 on the torques.)"""
-    import ctypes as C
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -489,29 +423,19 @@ def test_no_unwritten_storage_feeds_the_arithmetic(tmp_path):
     libs = []
     for so, proc in builds:
         assert proc.wait() == 0
-        libs.append(C.CDLL(so))
-    dp = C.POINTER(C.c_double)
+        libs.append(ht.bind(so))
     names = ("Kp_body_p", "Kd_body_p", "Kp_body_rpy", "Kd_body_rpy", "Kp_foot", "Kd_foot", "w_body", "w_foot", "mu", "Kd_contact", "tau_max", "tiebreak_eps2")
     n = 128
-    for cfg, kind, k, tmax in ((2, "clf", 3, None), (3, "clf", 3, None), (2, "pc", 2, None), (3, "pc", 2, None), (2, "id", 0, None), (2, "mptc", 1, None),
-                               (3, "mptc", 1, None), (2, "clf", 3, 12.0), (2, "id", 0, 8.0)):
+    for cfg, kind, tmax in ((2, "clf", None), (3, "clf", None), (2, "pc", None), (3, "pc", None), (2, "id", None), (2, "mptc", None),
+                            (3, "mptc", None), (2, "clf", 12.0), (2, "id", 8.0)):
         b = workloads.make_batch(cfg, n=n)
         t = orc.load_model_json(b["model"])
         pp = None
         if tmax is not None:
             p = orc.params(kind); p.tau_max = tmax
             pp = np.array([getattr(p, f) for f in names], dtype=np.float64)
-        q, v, tg = (np.ascontiguousarray(b[x]) for x in ("q", "v", "targets"))
-        flat = np.ascontiguousarray(t["flat"], dtype=np.float64)
-        out = []
-        for L in libs:
-            tau = np.zeros((12, n)); met = np.zeros((4, n)); st = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
-            rc = L.host_hex_batch(k, flat.ctypes.data_as(dp), pp.ctypes.data_as(dp) if pp is not None else None, None, None, n, n, q.ctypes.data_as(dp),
-                                  v.ctypes.data_as(dp), tg.ctypes.data_as(dp), b["mask"].ctypes.data_as(C.POINTER(C.c_ubyte)), None, None,
-                                  tau.ctypes.data_as(dp), met.ctypes.data_as(dp), st.ctypes.data_as(C.POINTER(C.c_int)), it.ctypes.data_as(C.POINTER(C.c_int)))
-            assert rc == 0
-            out.append((tau, met, st, it))
-        (tau, met, st, it), (tau_p, met_p, st_p, it_p) = out
+        (tau, met, st, it), (tau_p, met_p, st_p, it_p) = (
+            ht.run(kind, t["flat"], b["q"], b["v"], b["targets"], b["mask"], params12=pp, hexv=True, lib=L) for L in libs)
         assert np.isfinite(tau_p).all() and np.isfinite(met_p).all(), (cfg, kind, int(np.isnan(tau_p).any(0).sum()))
         assert np.array_equal(st, st_p) and np.array_equal(it, it_p), (cfg, kind, tmax)
         assert np.array_equal(tau, tau_p) and np.array_equal(met, met_p), (cfg, kind, tmax)
@@ -523,20 +447,12 @@ def test_closed_switches_patch_applies_and_is_neutral(tmp_path):
     """tools/lab/patches/closed_switches.patch puts the compile-time switches of rounds 1-5 (alternatives that were measured and closed; removed from
     the product source in round 6) back into a copy of the headers.  It must apply to the current tree, and without any -D flag the patched tree must
     still be the product's arithmetic: same bits as the ordinary host build on a stand and a trot of every law."""
-    import ctypes as C
     L = ht.build_variant(tmp_path, "libhost_patched.so", [])
-    dp = C.POINTER(C.c_double)
     n = 48
     for cfg in (2, 3):
         b = workloads.make_batch(cfg, n=n)
         t = orc.load_model_json(b["model"])
-        q, v, tg = (np.ascontiguousarray(b[x]) for x in ("q", "v", "targets"))
-        flat = np.ascontiguousarray(t["flat"], dtype=np.float64)
-        for kind, k in (("id", 0), ("mptc", 1), ("pc", 2), ("clf", 3)):
-            tau = np.zeros((12, n)); met = np.zeros((4, n)); st = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
-            rc = L.host_hex_batch(k, flat.ctypes.data_as(dp), None, None, None, n, n, q.ctypes.data_as(dp), v.ctypes.data_as(dp), tg.ctypes.data_as(dp),
-                                  b["mask"].ctypes.data_as(C.POINTER(C.c_ubyte)), None, None, tau.ctypes.data_as(dp), met.ctypes.data_as(dp),
-                                  st.ctypes.data_as(C.POINTER(C.c_int)), it.ctypes.data_as(C.POINTER(C.c_int)))
-            assert rc == 0
+        for kind in ("id", "mptc", "pc", "clf"):
+            tau, met, st, it = ht.run(kind, t["flat"], b["q"], b["v"], b["targets"], b["mask"], hexv=True, lib=L)
             tau_g, met_g, st_g, it_g = ht.run(kind, t["flat"], b["q"], b["v"], b["targets"], b["mask"], hexv=True)
             assert np.array_equal(tau, tau_g) and np.array_equal(met, met_g) and np.array_equal(st, st_g) and np.array_equal(it, it_g), (cfg, kind)

@@ -120,7 +120,6 @@ def test_hinted_index_search_equals_numpy_argmin():
     import ctypes as C
     import host_tick as ht
     L = ht.lib()
-    L.host_traj_index.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.c_int]
     rng = np.random.default_rng(5)
     for trial in range(40):
         K = int(rng.integers(1, 60))

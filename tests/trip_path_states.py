@@ -44,10 +44,8 @@ def first_picks(kind, q, v, tg, mask):
     n = q.shape[1]
     L = ht.lib()
     buf = np.zeros((n, 16, 16))
-    L.host_gi_dump.argtypes = [C.c_void_p]
     L.host_gi_dump(buf.ctypes.data_as(C.c_void_p))
     adds = np.zeros((n, 32), np.int32)
-    L.host_gi_adds.argtypes = [C.c_void_p]
     L.host_gi_adds(adds.ctypes.data_as(C.c_void_p))
     try:
         out = ht.run(kind, orc.load_model_json("mini_cheetah")["flat"], q, v, tg, mask, hexv=True)
