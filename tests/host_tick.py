@@ -72,33 +72,35 @@ def build_variant(tmp_path, name, flags, compiler=None):
     return bind(so)
 
 
-def _p(a):
-    return a.ctypes.data_as(_dp) if a is not None else None
+def _p(a, dtype=np.float64):
+    """`a` (or None) as the contiguous array of `dtype` the ABI reads and the pointer to it; the array must outlive the call."""
+    if a is None:
+        return None, None
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return a, a.ctypes.data_as({np.float64: _dp, np.int32: _ip, np.uint8: _mp}[dtype])
+
+
+def _batch(kind, flat, q, v, targets, mask, mu, mass_scale):
+    """What run and count marshal alike: the law's number, n, the arrays kept alive, and the pointers flat | q, v, targets, mask, mu, mass_scale."""
+    k = {"id": 0, "mptc": 1, "pc": 2, "clf": 3}[kind.lower()] if isinstance(kind, str) else int(kind)
+    pairs = [_p(a) for a in (flat, q, v, targets)] + [_p(mask, np.uint8), _p(mu), _p(mass_scale)]
+    ptrs = [p for _, p in pairs]
+    return k, pairs[1][0].shape[1], pairs, ptrs[0], ptrs[1:]
 
 
 def run(kind, flat, q, v, targets, mask, mu=None, mass_scale=None, params12=None, q_perm=None, act_perm=None,
         want_vdot=False, hexv=False, lib=None):
     """One batch through host_tick_batch (hexv: host_hex_batch) of `lib` (None: the default build) -> tau, met, status, iters[, vdot]"""
     L = _default() if lib is None else lib
-    q, v, targets = (np.ascontiguousarray(a, dtype=np.float64) for a in (q, v, targets))
-    mask = np.ascontiguousarray(mask, dtype=np.uint8)
-    flat = np.ascontiguousarray(flat, dtype=np.float64)
-    n = q.shape[1]
+    k, n, _keep, flat_p, batch_p = _batch(kind, flat, q, v, targets, mask, mu, mass_scale)
     tau = np.zeros((12, n)); met = np.zeros((4, n)); st = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
-    mu = None if mu is None else np.ascontiguousarray(mu, dtype=np.float64)
-    ms = None if mass_scale is None else np.ascontiguousarray(mass_scale, dtype=np.float64)
-    pp = None if params12 is None else np.ascontiguousarray(params12, dtype=np.float64)
-    qp = None if q_perm is None else np.ascontiguousarray(q_perm, dtype=np.int32)
-    ap = None if act_perm is None else np.ascontiguousarray(act_perm, dtype=np.int32)
-    k = {"id": 0, "mptc": 1, "pc": 2, "clf": 3}[kind.lower()] if isinstance(kind, str) else int(kind)
+    extra = [_p(params12), _p(q_perm, np.int32), _p(act_perm, np.int32)]
     vdot = np.zeros((18, n)) if want_vdot else None
     if want_vdot:                                    # (a HEX_ONLY variant has no sink)
         L.host_set_vdot_sink(vdot.ctypes.data_as(C.c_void_p))
     fn = L.host_hex_batch if hexv else L.host_tick_batch
     try:
-        rc = fn(k, _p(flat), _p(pp), qp.ctypes.data_as(_ip) if qp is not None else None, ap.ctypes.data_as(_ip) if ap is not None else None,
-                n, n, _p(q), _p(v), _p(targets), mask.ctypes.data_as(_mp), _p(mu), _p(ms), _p(tau), _p(met), st.ctypes.data_as(_ip),
-                it.ctypes.data_as(_ip))
+        rc = fn(k, flat_p, *[p for _, p in extra], n, n, *batch_p, _p(tau)[1], _p(met)[1], _p(st, np.int32)[1], _p(it, np.int32)[1])
     finally:
         if want_vdot:
             L.host_set_vdot_sink(None)
@@ -107,15 +109,8 @@ def run(kind, flat, q, v, targets, mask, mu=None, mass_scale=None, params12=None
 
 
 def count(kind, flat, q, v, targets, mask, mu=None, mass_scale=None):
-    q, v, targets = (np.ascontiguousarray(a, dtype=np.float64) for a in (q, v, targets))
-    mask = np.ascontiguousarray(mask, dtype=np.uint8)
-    flat = np.ascontiguousarray(flat, dtype=np.float64)
-    n = q.shape[1]
+    k, n, _keep, flat_p, batch_p = _batch(kind, flat, q, v, targets, mask, mu, mass_scale)
     out = np.zeros(6)
-    mu = None if mu is None else np.ascontiguousarray(mu, dtype=np.float64)
-    ms = None if mass_scale is None else np.ascontiguousarray(mass_scale, dtype=np.float64)
-    k = {"id": 0, "mptc": 1, "pc": 2, "clf": 3}[kind.lower()] if isinstance(kind, str) else int(kind)
-    rc = lib().host_tick_count(k, _p(flat), None, n, n, _p(q), _p(v), _p(targets),
-                               mask.ctypes.data_as(_mp), _p(mu), _p(ms), _p(out))
+    rc = lib().host_tick_count(k, flat_p, None, n, n, *batch_p, _p(out)[1])
     assert rc == 0
     return dict(zip(["add", "mul", "div", "sqrt", "trig", "cmp"], out))

@@ -4,10 +4,13 @@
 //   * with an operation-counting scalar, which yields the frozen flops/tick figure that
 //     bench.py's roofline uses.
 // The shipped library (libwbc_hip.so) never calls this; it has no CPU path.
+// Every exported call builds its own context and remembers nothing afterwards.  What is left of process state are the diagnostic hooks
+// that wbc_hex.hpp declares as plain globals (g_gi_*, set through host_gi_*) and the vdot sink, so two threads must not call in at once.
 #include <math.h>
-#include <stdlib.h>
 #include <atomic>
+#include <memory>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include <stdint.h>
 #include <string.h>
@@ -39,24 +42,60 @@ template <> double val<Cnt>(const Cnt& x) { return x.v; }
 
 static double* g_vdot = nullptr;  // optional [18][stride] sink for the generalized accelerations (rows 4..21 of out_met)
 
-template <class T>
-static int run_one(int kind, const wbc::ModelC& m, const wbc::ParamsC& P, int i, int stride, const double* q,
-                   const double* v, const double* tg, unsigned mask, double mu, double ms, double* tau,
-                   double* met, int* iters) {
-  auto in = [&](int r) -> T {
+// One instance seen through the strided ABI: inputs are element i of rows `stride` wide (q 19 | v 18 | targets), outputs element o of rows
+// `ostride` wide.  Rows 0..3 of out_met are the metrics, 4..21 the generalized accelerations, kept only where this call has a sink.  h: the
+// calling lane of the 16-lane tick, whose lane 0 writes what is replicated (rows 10..21 of out_met are lane-owned); the scalar tick is lane 0.
+struct Io {
+  const double *q, *v, *tg; int stride, i;
+  double *tau, *met, *vdot; int ostride, o;
+  template <class T> T in(int r) const {
     if (r < 19) return T(q[(size_t)r * stride + i]);
     if (r < 37) return T(v[(size_t)(r - 19) * stride + i]);
     return T(tg[(size_t)(r - 37) * stride + i]);
-  };
-  auto ot = [&](int k, T x) { tau[(size_t)k * stride + i] = val<T>(x); };
-  auto om = [&](int k, T x) {
-    if (k >= 4) { if (g_vdot) g_vdot[(size_t)(k - 4) * stride + i] = val<T>(x); return; }
-    if (met) met[(size_t)k * stride + i] = val<T>(x);
-  };
-  if (kind == wbc::KIND_ID) return wbc::tick<T, wbc::KIND_ID>(m, P, in, mask, T(mu), T(ms), ot, om, iters);
-  if (kind == wbc::KIND_PC) return wbc::tick<T, wbc::KIND_PC>(m, P, in, mask, T(mu), T(ms), ot, om, iters);
-  if (kind == wbc::KIND_CLF) return wbc::tick<T, wbc::KIND_CLF>(m, P, in, mask, T(mu), T(ms), ot, om, iters);
-  return wbc::tick<T, wbc::KIND_MPTC>(m, P, in, mask, T(mu), T(ms), ot, om, iters);
+  }
+  template <class T> void out_tau(int k, const T& x) const { tau[(size_t)k * ostride + o] = val<T>(x); }
+  template <class T> void out_met(int k, const T& x, int h = 0) const {
+    if (k >= 4) { if (vdot && (k >= 10 || h == 0)) vdot[(size_t)(k - 4) * ostride + o] = val<T>(x); return; }
+    if (met && h == 0) met[(size_t)k * ostride + o] = val<T>(x);
+  }
+};
+
+// The one map from a law (and, for the 16-lane tick, torque box and warm start) to its instantiation: f gets them as integral constants.
+template <class F> static int for_law(int kind, F&& f) {
+  if (kind == wbc::KIND_ID) return f(std::integral_constant<int, wbc::KIND_ID>{});
+  if (kind == wbc::KIND_PC) return f(std::integral_constant<int, wbc::KIND_PC>{});
+  if (kind == wbc::KIND_CLF) return f(std::integral_constant<int, wbc::KIND_CLF>{});
+  return f(std::integral_constant<int, wbc::KIND_MPTC>{});
+}
+template <class F> static int for_law(int kind, bool tb, bool warm, F&& f) {
+  return for_law(kind, [&](auto K) {
+    auto w = [&](auto TB) {
+#ifndef HOST_TICK_HEX_ONLY
+      if (warm) return f(K, TB, std::true_type{});
+#else   // (the variant builds of tests/host_tick.py::build_variant only run cold ticks: a third of the compile time)
+      if (warm) return (int)wbc::ST_SINGULAR;
+#endif
+      return f(K, TB, std::false_type{});
+    };
+    return tb ? w(std::true_type{}) : w(std::false_type{});
+  });
+}
+
+// model, perms and the twelve parameters (NULL = the reference defaults) of a call
+static int setup(int kind, const double* flat215, const double* params12, const int* q_perm, const int* act_perm, wbc::ModelC* m, wbc::ParamsC* P) {
+  if (wbc::model_from_flat(flat215, m)) return -1;
+  wbc::model_set_perms(m, q_perm, act_perm);
+  wbc::params_default(kind, P);
+  if (params12) memcpy(P, params12, sizeof(double) * 12);
+  return 0;
+}
+
+template <class T>
+static int run_one(int kind, const wbc::ModelC& m, const wbc::ParamsC& P, const Io& io, unsigned mask, double mu, double ms, int* iters) {
+  auto in = [&](int r) { return io.in<T>(r); };
+  auto ot = [&](int k, T x) { io.out_tau(k, x); };
+  auto om = [&](int k, T x) { io.out_met(k, x); };
+  return for_law(kind, [&](auto K) { return wbc::tick<T, decltype(K)::value>(m, P, in, mask, T(mu), T(ms), ot, om, iters); });
 }
 
 #ifndef HOST_TICK_HEX_ONLY   // (the variant builds of tests/host_tick.py::build_variant only call host_hex_batch: a third of the compile time)
@@ -69,15 +108,13 @@ int host_tick_batch(int kind, const double* flat215, const double* params12, con
                     const double* tg, const unsigned char* mask, const double* mu, const double* mass_scale,
                     double* tau, double* met, int* status, int* iters) {
   wbc::ModelC m;
-  if (wbc::model_from_flat(flat215, &m)) return -1;
-  wbc::model_set_perms(&m, q_perm, act_perm);
   wbc::ParamsC P;
-  wbc::params_default(kind, &P);
-  if (params12) memcpy(&P, params12, sizeof(double) * 12);
+  if (setup(kind, flat215, params12, q_perm, act_perm, &m, &P)) return -1;
+  double* const vdot = g_vdot;
   for (int i = 0; i < n; i++) {
     int it = 0;
-    int st = run_one<double>(kind, m, P, i, stride, q, v, tg, mask[i], mu ? mu[i] : P.mu,
-                             mass_scale ? mass_scale[i] : 1.0, tau, met, &it);
+    int st = run_one<double>(kind, m, P, Io{q, v, tg, stride, i, tau, met, vdot, stride, i}, mask[i], mu ? mu[i] : P.mu,
+                             mass_scale ? mass_scale[i] : 1.0, &it);
     if (status) status[i] = st;
     if (iters) iters[i] = it;
   }
@@ -88,28 +125,30 @@ void host_set_vdot_sink(double* vdot) { g_vdot = vdot; }
 
 // Timing driver for bench.py's cpu_baseline.reduced: `reps` passes over the n instances of the REDUCED algorithm the kernels run (12-variable QP, QR +
 // Goldfarb-Idnani: the scalar one-robot instantiation of tools/wbc_scalar_tick.hpp), instances dealt to `nthreads` std::threads in contiguous chunks.
-// Outputs of the last pass are kept.  Context beside the literal dense port of oracle/, never the thing measured or shipped.
+// Only the last pass writes the caller's tau / status (every chunk of it is one thread's); the passes before it write a thread's own one-instance
+// scratch, so a thread that is a pass behind shares no output with one that is ahead.  Context beside the literal dense port of oracle/, never the
+// thing measured or shipped.
 int host_tick_bench(int kind, const double* flat215, int n, int stride, const double* q, const double* v, const double* tg,
                     const unsigned char* mask, const double* mu, const double* mass_scale, double* tau, int* status, int nthreads, int reps) {
   wbc::ModelC m;
-  if (wbc::model_from_flat(flat215, &m) || g_vdot) return -1;
-  wbc::model_set_perms(&m, nullptr, nullptr);
   wbc::ParamsC P;
-  wbc::params_default(kind, &P);
+  if (g_vdot || setup(kind, flat215, nullptr, nullptr, nullptr, &m, &P)) return -1;
   if (nthreads < 1) nthreads = 1;
-  std::vector<double> met((size_t)4 * stride);
   // chunks of 8 instances (one cache line of every output row) handed out by an atomic counter: the oracle's `schedule(dynamic, 8)`
   std::atomic<long long> next{0};
   const long long chunks_per_pass = (n + 7) / 8, total = chunks_per_pass * reps;
   auto work = [&](int) {
+    double tau1[12], met1[4];
     for (;;) {
       const long long c = next.fetch_add(1);
       if (c >= total) break;
+      const bool last = c >= total - chunks_per_pass;
       const int lo = (int)(c % chunks_per_pass) * 8, hi = lo + 8 < n ? lo + 8 : n;
       for (int i = lo; i < hi; i++) {
         int it = 0;
-        const int st = run_one<double>(kind, m, P, i, stride, q, v, tg, mask[i], mu ? mu[i] : P.mu, mass_scale ? mass_scale[i] : 1.0, tau, met.data(), &it);
-        if (status) status[i] = st;
+        const Io io = last ? Io{q, v, tg, stride, i, tau, nullptr, nullptr, stride, i} : Io{q, v, tg, stride, i, tau1, met1, nullptr, 1, 0};
+        const int st = run_one<double>(kind, m, P, io, mask[i], mu ? mu[i] : P.mu, mass_scale ? mass_scale[i] : 1.0, &it);
+        if (last && status) status[i] = st;
       }
     }
   };
@@ -125,38 +164,20 @@ int host_tick_count(int kind, const double* flat215, const double* params12, int
                     const double* q, const double* v, const double* tg, const unsigned char* mask,
                     const double* mu, const double* mass_scale, double* out6) {
   wbc::ModelC m;
-  if (wbc::model_from_flat(flat215, &m)) return -1;
   wbc::ParamsC P;
-  wbc::params_default(kind, &P);
-  if (params12) memcpy(&P, params12, sizeof(double) * 12);
+  if (setup(kind, flat215, params12, nullptr, nullptr, &m, &P)) return -1;
   for (int k = 0; k < 6; k++) Cnt::c[k] = 0;
-  double tau[12 * 1], met[4];
   for (int i = 0; i < n; i++) {
     int it = 0;
-    double t1[12], m1[4];
-    // write outputs to a private 1-wide scratch (stride trick: use i=0, own buffers)
-    auto in = [&](int r) -> Cnt {
-      if (r < 19) return Cnt(q[(size_t)r * stride + i]);
-      if (r < 37) return Cnt(v[(size_t)(r - 19) * stride + i]);
-      return Cnt(tg[(size_t)(r - 37) * stride + i]);
-    };
-    auto ot = [&](int k, Cnt x) { t1[k] = x.v; };
-    auto om = [&](int k, Cnt x) { if (k < 4) m1[k] = x.v; };
-    Cnt muv(mu ? mu[i] : P.mu), msv(mass_scale ? mass_scale[i] : 1.0);
-    if (kind == wbc::KIND_ID) wbc::tick<Cnt, wbc::KIND_ID>(m, P, in, mask[i], muv, msv, ot, om, &it);
-    else if (kind == wbc::KIND_PC) wbc::tick<Cnt, wbc::KIND_PC>(m, P, in, mask[i], muv, msv, ot, om, &it);
-    else if (kind == wbc::KIND_CLF) wbc::tick<Cnt, wbc::KIND_CLF>(m, P, in, mask[i], muv, msv, ot, om, &it);
-    else wbc::tick<Cnt, wbc::KIND_MPTC>(m, P, in, mask[i], muv, msv, ot, om, &it);
+    double t1[12], m1[4];   // the outputs go to a one-instance scratch
+    run_one<Cnt>(kind, m, P, Io{q, v, tg, stride, i, t1, m1, nullptr, 1, 0}, mask[i], mu ? mu[i] : P.mu, mass_scale ? mass_scale[i] : 1.0, &it);
   }
-  (void)tau; (void)met;
   for (int k = 0; k < 6; k++) out6[k] = (double)Cnt::c[k] / n;
   return 0;
 }
 }
 
 #endif   // HOST_TICK_HEX_ONLY
-
-#include <vector>
 
 // ---------------------------------------------------------------------------------------------
 // Host emulation of the 16-lanes-per-robot kernel (wbc_hex.hpp): 16 cooperative fibres (ucontext,
@@ -180,52 +201,39 @@ extern "C" void host_gi_stats(int* out, int reset) {
 #include "../quadruped_drake_amd/csrc/wbc_hex.hpp"
 
 namespace {
-struct HexCtx {
+struct HexCtx {   // the fibre scheduler of one call
   double slot[16];
   int islot[16];
   int count = 0;
   unsigned gen = 0;
   ucontext_t ctx[16], main;
   bool finished[16];
-  int cur = 0;
-  void (*body)(int) = nullptr;
-};
-HexCtx* g_hex = nullptr;
-
-void hex_switch_from(int me) {
-  HexCtx* c = g_hex;
-  for (int d = 1; d <= 16; d++) {
-    const int nx = (me + d) % 16;
-    if (!c->finished[nx]) {
-      if (nx == me) return;
-      c->cur = nx;
-      swapcontext(&c->ctx[me], &c->ctx[nx]);
-      return;
+  void switch_from(int me) {
+    for (int d = 1; d <= 16; d++) {
+      const int nx = (me + d) % 16;
+      if (!finished[nx]) {
+        if (nx != me) swapcontext(&ctx[me], &ctx[nx]);
+        return;
+      }
     }
+    swapcontext(&ctx[me], &main);  // everybody finished
   }
-  swapcontext(&c->ctx[me], &c->main);  // everybody finished
-}
-void hex_barrier(int me) {
-  HexCtx* c = g_hex;
-  const unsigned g = c->gen;
-  if (++c->count == 16) { c->count = 0; c->gen++; return; }
-  while (c->gen == g) hex_switch_from(me);
-}
-void hex_entry(int lane) {
-  HexCtx* c = g_hex;
-  c->body(lane);
-  hex_barrier(lane);  // all lanes leave together
-  c->finished[lane] = true;
-  hex_switch_from(lane);
-}
+  void barrier(int me) {
+    const unsigned g = gen;
+    if (++count == 16) { count = 0; gen++; return; }
+    while (gen == g) switch_from(me);
+  }
+};
 }  // namespace
 
 struct HexHost {
   int h;
+  HexCtx* c;
   int lane() const { return h; }
+  void bar() { c->barrier(h); }
   double xchg(double x, int src) {
-    g_hex->slot[h] = x; hex_barrier(h);
-    const double r = g_hex->slot[src]; hex_barrier(h);
+    c->slot[h] = x; bar();
+    const double r = c->slot[src]; bar();
     return r;
   }
   double bcast16(double x, int src) { return xchg(x, src); }
@@ -247,158 +255,154 @@ struct HexHost {
   double leg_pairs(double x) { return xchg(x, (h & ~3) | ((h & 3) >> 1)); }   // quad_perm [0,0,1,1]
   double bcast16d(double x, int src) { return xchg(x, src); }                  // dynamic (robot-uniform) source lane
   int bcast16d_i(int x, int src) {
-    g_hex->islot[h] = x; hex_barrier(h);
-    const int r = g_hex->islot[src]; hex_barrier(h);
+    c->islot[h] = x; bar();
+    const int r = c->islot[src]; bar();
     return r;
   }
   static double quad_of(const double* s, int b) { return (s[b] + s[b ^ 1]) + (s[b ^ 2] + s[b ^ 3]); }
   double leg_sum(double x) {
-    g_hex->slot[h] = x; hex_barrier(h);
-    const double r = quad_of(g_hex->slot, h); hex_barrier(h);
+    c->slot[h] = x; bar();
+    const double r = quad_of(c->slot, h); bar();
     return r;
   }
   double legs_sum(double x) {
-    g_hex->slot[h] = x; hex_barrier(h);
-    const double* s = g_hex->slot;
-    const double r = (s[h] + s[h ^ 8]) + (s[h ^ 4] + s[h ^ 12]); hex_barrier(h);
+    c->slot[h] = x; bar();
+    const double* s = c->slot;
+    const double r = (s[h] + s[h ^ 8]) + (s[h ^ 4] + s[h ^ 12]); bar();
     return r;
   }
   template <int N> void legs_sum_n(double* x) {   // device: v_mov_b64_dpp + 3 fused broadcast-FMAs per value (sub-lane 0 of each leg)
     for (int i = 0; i < N; i++) {
-      g_hex->slot[h] = x[i]; hex_barrier(h);
-      const double* s = g_hex->slot;
-      const double r = ((s[0] + s[4]) + s[8]) + s[12]; hex_barrier(h);
+      c->slot[h] = x[i]; bar();
+      const double* s = c->slot;
+      const double r = ((s[0] + s[4]) + s[8]) + s[12]; bar();
       x[i] = r;
     }
   }
   double sum16(double x) {
-    g_hex->slot[h] = x; hex_barrier(h);
-    const double* s = g_hex->slot;
-    const double r = (quad_of(s, h) + quad_of(s, h ^ 8)) + (quad_of(s, h ^ 4) + quad_of(s, h ^ 12)); hex_barrier(h);
+    c->slot[h] = x; bar();
+    const double* s = c->slot;
+    const double r = (quad_of(s, h) + quad_of(s, h ^ 8)) + (quad_of(s, h ^ 4) + quad_of(s, h ^ 12)); bar();
     return r;
   }
   double min16(double x) {
-    g_hex->slot[h] = x; hex_barrier(h);
-    double r = g_hex->slot[0];
-    for (int k = 1; k < 16; k++) r = fmin(r, g_hex->slot[k]);
-    hex_barrier(h);
+    c->slot[h] = x; bar();
+    double r = c->slot[0];
+    for (int k = 1; k < 16; k++) r = fmin(r, c->slot[k]);
+    bar();
     return r;
   }
   double max16(double x) {
-    g_hex->slot[h] = x; hex_barrier(h);
-    double r = g_hex->slot[0];
-    for (int k = 1; k < 16; k++) r = fmax(r, g_hex->slot[k]);
-    hex_barrier(h);
+    c->slot[h] = x; bar();
+    double r = c->slot[0];
+    for (int k = 1; k < 16; k++) r = fmax(r, c->slot[k]);
+    bar();
     return r;
   }
   bool any16(bool b) {
-    g_hex->islot[h] = b; hex_barrier(h);
+    c->islot[h] = b; bar();
     bool r = false;
-    for (int k = 0; k < 16; k++) r |= (g_hex->islot[k] != 0);
-    hex_barrier(h);
+    for (int k = 0; k < 16; k++) r |= (c->islot[k] != 0);
+    bar();
     return r;
   }
   void argmin16(double& v, int& i) {
-    g_hex->slot[h] = v; g_hex->islot[h] = i; hex_barrier(h);
-    double bv = g_hex->slot[0]; int bi = g_hex->islot[0];
+    c->slot[h] = v; c->islot[h] = i; bar();
+    double bv = c->slot[0]; int bi = c->islot[0];
     for (int k = 1; k < 16; k++) {
-      const double ov = g_hex->slot[k]; const int oi = g_hex->islot[k];
+      const double ov = c->slot[k]; const int oi = c->islot[k];
       if (ov < bv || (ov == bv && oi >= 0 && (bi < 0 || oi < bi))) { bv = ov; bi = oi; }
     }
-    hex_barrier(h);
+    bar();
     v = bv; i = bi;
   }
   bool wave_all(bool b) { return b; }
-  bool wave_any(bool b) { return getenv("WBC_ANY_TRUE") ? true : b; }
+  bool wave_any(bool b) { return b; }
   int wave_max_int(int x) { return x; }
 };
 
-// warm start of the emulated rollout (host_hex_rollout): the per-lane seed bit of hex_gi<..., WARM> between the ticks of ONE robot
-static int g_hex_warm = 0;
-static bool g_hex_seed[16];
+namespace {
+// What one exported call of the emulation owns: model, parameters, scheduler, fibre stacks, the park storage of the robot that is running (the
+// device's LDS), the warm start's per-lane seed bits (hex_gi<..., WARM>) and the instance the 16 lanes are working on.
+struct HexCall;
+thread_local HexCall* t_call = nullptr;   // makecontext passes ints only: a fibre finds its call here, for as long as the call lasts
+struct HexCall {
+  static constexpr size_t STK = 1 << 20;
+  wbc::ModelC m;
+  wbc::ParamsC P0;
+  wbc::ParamsX P;
+  HexCtx fib;
+  std::unique_ptr<char[]> stacks{new char[16 * STK]};
+  wbc::ParkHost pk[16];
+  int kind;
+  bool warm = false, seed[16];
+  Io io; unsigned mask; double mu, ms; int *status, *iters;   // the instance that is running
+  HexCall() { t_call = this; }
+  ~HexCall() { t_call = nullptr; }
+  int init(int kind_, const double* flat215, const double* params12, const int* q_perm, const int* act_perm) {
+    kind = kind_;
+    if (setup(kind, flat215, params12, q_perm, act_perm, &m, &P0)) return -1;
+    wbc::params_derive(P0, &P);
+    return 0;
+  }
+  void lane(int h) {
+    HexHost qo{h, &fib};
+    auto in = [&](int r) { return io.in<double>(r); };
+    auto ot = [&](int k, double x) { io.out_tau(k, x); };
+    auto om = [&](int k, double x) { io.out_met(k, x, h); };
+    int it = 0;
+    bool sd = seed[h];   // WARM: this lane's friction row was active when the robot's previous tick ended
+    const int st = for_law(kind, P.tau_max < 1e300, warm, [&](auto K, auto TB, auto W) {
+      return wbc::hex_tick<HexHost, decltype(K)::value, decltype(TB)::value, decltype(W)::value>(m, P, qo, in, mask, mu, ms, pk[h], ot, om, &it,
+                                                                                               decltype(W)::value ? &sd : nullptr);
+    });
+    if (warm) seed[h] = (st == wbc::ST_OK) && sd;
+    if (h == 0) { if (status) *status = st; if (iters) *iters = it; }
+  }
+  static void entry(int h) {
+    HexCall* c = t_call;
+    c->lane(h);
+    c->fib.barrier(h);  // all lanes leave together
+    c->fib.finished[h] = true;
+    c->fib.switch_from(h);
+  }
+  // One tick of one robot on the 16 fibres.  first: the robot's first tick of this call, which starts on park storage nobody has written (all-ones
+  // bytes, a NaN, as the device's LDS is unwritten there) and without seeds; later ticks of a rollout find both as the previous one left them,
+  // as wbc_hex_rollout_kernel does.  hook_row: the robot's row in the buffers of host_gi_dump / host_gi_adds.
+  void tick(const Io& io_, unsigned mask_, double mu_, double ms_, int* status_, int* iters_, int hook_row, bool first) {
+    io = io_; mask = mask_ & 0xFu; mu = mu_; ms = ms_; status = status_; iters = iters_;
+    if (first) {
+      memset(pk, 0xFF, sizeof(pk));
+      for (int h = 0; h < 16; h++) seed[h] = false;
+    }
+    g_gi_dump = g_gi_dump_base ? g_gi_dump_base + (size_t)hook_row * 256 : nullptr;
+    g_gi_adds = g_gi_adds_base ? g_gi_adds_base + (size_t)hook_row * 32 : nullptr;
+    fib.count = 0;
+    for (int h = 0; h < 16; h++) {
+      fib.finished[h] = false;
+      getcontext(&fib.ctx[h]);
+      fib.ctx[h].uc_stack.ss_sp = stacks.get() + (size_t)h * STK;
+      fib.ctx[h].uc_stack.ss_size = STK;
+      fib.ctx[h].uc_link = &fib.main;
+      makecontext(&fib.ctx[h], (void (*)())entry, 1, h);
+    }
+    swapcontext(&fib.main, &fib.ctx[0]);
+  }
+};
+}  // namespace
 
 extern "C" int host_hex_batch(int kind, const double* flat215, const double* params12, const int* q_perm,
                               const int* act_perm, int n, int stride, const double* q, const double* v,
                               const double* tg, const unsigned char* mask, const double* mu,
                               const double* mass_scale, double* tau, double* met, int* status, int* iters) {
-  static wbc::ModelC m;
-  static wbc::ParamsC P0;
-  static wbc::ParamsX P;
-  if (wbc::model_from_flat(flat215, &m)) return -1;
-  wbc::model_set_perms(&m, q_perm, act_perm);
-  wbc::params_default(kind, &P0);
-  if (params12) memcpy(&P0, params12, sizeof(double) * 12);
-  wbc::params_derive(P0, &P);
-  static HexCtx ctx;
-  g_hex = &ctx;
-  const size_t STK = 1 << 20;
-  static std::vector<char> stacks(16 * STK);
-  static wbc::ParkHost pk[16];
-  struct Args { int kind, i, stride; const double *q, *v, *tg, *mu, *ms; const unsigned char* mask; double *tau, *met; int *status, *iters; };
-  static Args A;
-  A = Args{kind, 0, stride, q, v, tg, mu, mass_scale, mask, tau, met, status, iters};
-  ctx.body = [](int h) {
-    const Args& a = A;
-    const int i = a.i;
-    HexHost qo{h};
-    auto in = [&](int r) -> double {
-      if (r < 19) return a.q[(size_t)r * a.stride + i];
-      if (r < 37) return a.v[(size_t)(r - 19) * a.stride + i];
-      return a.tg[(size_t)(r - 37) * a.stride + i];
-    };
-    auto ot = [&](int k, double x) { a.tau[(size_t)k * a.stride + i] = x; };
-    auto om = [&](int k, double x) {
-      if (k >= 4) { if (g_vdot && (k >= 10 || h == 0)) g_vdot[(size_t)(k - 4) * a.stride + i] = x; return; }
-      if (h == 0 && a.met) a.met[(size_t)k * a.stride + i] = x;
-    };
-    int it = 0, st;
-    const double mui = a.mu ? a.mu[i] : P.mu, msi = a.ms ? a.ms[i] : 1.0;
-    const bool tb = P.tau_max < 1e300;
-#define HEX_RUN(K) (tb ? wbc::hex_tick<HexHost, K, true>(m, P, qo, in, a.mask[i] & 0xFu, mui, msi, pk[h], ot, om, &it) \
-                       : wbc::hex_tick<HexHost, K, false>(m, P, qo, in, a.mask[i] & 0xFu, mui, msi, pk[h], ot, om, &it))
-    if (!g_hex_warm) {
-      if (a.kind == wbc::KIND_ID) st = HEX_RUN(wbc::KIND_ID);
-      else if (a.kind == wbc::KIND_PC) st = HEX_RUN(wbc::KIND_PC);
-      else if (a.kind == wbc::KIND_CLF) st = HEX_RUN(wbc::KIND_CLF);
-      else st = HEX_RUN(wbc::KIND_MPTC);
-    } else {
-#ifndef HOST_TICK_HEX_ONLY
-      // the rollout kernels' instantiation (WARM): this lane's friction row was active when the robot's previous tick ended
-      bool sd = g_hex_seed[h];
-#define HEX_RUN_W(K) (tb ? wbc::hex_tick<HexHost, K, true, true>(m, P, qo, in, a.mask[i] & 0xFu, mui, msi, pk[h], ot, om, &it, &sd) \
-                         : wbc::hex_tick<HexHost, K, false, true>(m, P, qo, in, a.mask[i] & 0xFu, mui, msi, pk[h], ot, om, &it, &sd))
-      if (a.kind == wbc::KIND_ID) st = HEX_RUN_W(wbc::KIND_ID);
-      else if (a.kind == wbc::KIND_PC) st = HEX_RUN_W(wbc::KIND_PC);
-      else if (a.kind == wbc::KIND_CLF) st = HEX_RUN_W(wbc::KIND_CLF);
-      else st = HEX_RUN_W(wbc::KIND_MPTC);
-#undef HEX_RUN_W
-      g_hex_seed[h] = (st == wbc::ST_OK) && sd;
-#else
-      st = wbc::ST_SINGULAR;   // (not part of a HOST_TICK_HEX_ONLY build)
-#endif
-    }
-#undef HEX_RUN
-    if (h == 0) { if (a.status) a.status[i] = st; if (a.iters) a.iters[i] = it; }
-  };
-  for (int i = 0; i < n; i++) {
-    A.i = i;
-    g_gi_dump = g_gi_dump_base ? g_gi_dump_base + (size_t)i * 256 : nullptr;
-    g_gi_adds = g_gi_adds_base ? g_gi_adds_base + (size_t)i * 32 : nullptr;
-    ctx.count = 0;
-    for (int h = 0; h < 16; h++) {
-      ctx.finished[h] = false;
-      getcontext(&ctx.ctx[h]);
-      ctx.ctx[h].uc_stack.ss_sp = stacks.data() + (size_t)h * STK;
-      ctx.ctx[h].uc_stack.ss_size = STK;
-      ctx.ctx[h].uc_link = &ctx.main;
-      makecontext(&ctx.ctx[h], (void (*)())hex_entry, 1, h);
-    }
-    ctx.cur = 0;
-    swapcontext(&ctx.main, &ctx.ctx[0]);
-  }
+  HexCall c;
+  if (c.init(kind, flat215, params12, q_perm, act_perm)) return -1;
+  double* const vdot = g_vdot;
+  for (int i = 0; i < n; i++)
+    c.tick(Io{q, v, tg, stride, i, tau, met, vdot, stride, i}, mask[i], mu ? mu[i] : c.P.mu, mass_scale ? mass_scale[i] : 1.0,
+           status ? status + i : nullptr, iters ? iters + i : nullptr, i, true);
   return 0;
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // Host instantiation of the hinted nearest-sample search of the persistent rollout (wbc_traj_dev.hpp).
@@ -410,25 +414,21 @@ extern "C" int host_hex_batch(int kind, const double* flat215, const double* par
 extern "C" int host_hex_rollout(int kind, const double* flat215, const double* params12, int n, int stride, int steps, double dt, int warm,
                                 double* q, double* v, const double* tg_seq, const unsigned char* masks, const double* mu, const double* mass_scale,
                                 double* tau, double* met, int* status, double* iters_sum, int* status_nonzero_ticks) {
-  double* const sink = g_vdot;
+  HexCall c;
+  if (c.init(kind, flat215, params12, nullptr, nullptr)) return -1;
+  c.warm = warm != 0;
   int bad_total = 0;
   for (int i = 0; i < n; i++) {
     double q1[19], v1[18], vd1[18], tau1[12], met1[4];
     for (int r = 0; r < 19; r++) q1[r] = q[(size_t)r * stride + i];
     for (int r = 0; r < 18; r++) v1[r] = v[(size_t)r * stride + i];
-    for (int h = 0; h < 16; h++) g_hex_seed[h] = false;
     int st1 = 0;
     double its = 0.0;
     for (int s = 0; s < steps; s++) {
       int it1 = 0;
       for (int r = 0; r < 18; r++) vd1[r] = 0.0;
-      g_vdot = vd1;
-      g_hex_warm = warm;
-      const int rc = host_hex_batch(kind, flat215, params12, nullptr, nullptr, 1, 1, q1, v1, tg_seq + (size_t)s * 54, masks + s, mu ? mu + i : nullptr,
-                                    mass_scale ? mass_scale + i : nullptr, tau1, met1, &st1, &it1);
-      g_hex_warm = 0;
-      g_vdot = sink;
-      if (rc) return rc;
+      c.tick(Io{q1, v1, tg_seq + (size_t)s * 54, 1, 0, tau1, met1, vd1, 1, 0}, masks[s], mu ? mu[i] : c.P.mu, mass_scale ? mass_scale[i] : 1.0,
+             &st1, &it1, 0, s == 0);
       its += it1;
       bad_total += (st1 != 0);
       // v+ = v + dt vd ; quat+ = exp(dt/2 w+) (x) quat, renormalised (wbc::quat_step) ; p, joints advance with v+

@@ -15,7 +15,6 @@ def dump(cfg, n, kind=None, seed=None):
     t = orc.load_model_json(b["model"])
     buf = np.zeros((n, 16, 16))
     L = ht.lib()
-    L.host_gi_dump.argtypes = [C.c_void_p]
     L.host_gi_dump(buf.ctypes.data_as(C.c_void_p))
     st = np.zeros(3, np.int32)
     L.host_gi_stats(st.ctypes.data_as(C.POINTER(C.c_int)), 1)
