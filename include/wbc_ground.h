@@ -41,8 +41,35 @@
  * contact bit c is phi > 0.  With g = 0 and H = 0 this is the law of the plane.  The integrator, the substeps and the stability
  * condition are untouched: the stiffness along n is still `stiffness`.  The limits of the model: the contact is first order in the
  * local plane (a foot near a convex knot feels the plane of the segment under it, extended); the normal jumps at a knot; there are
- * no overhangs and no contact with a riser's face from the side beyond what the steep segment gives; and the controllers still
- * assume a level ground -- their friction pyramids stay about world z.
+ * no overhangs and no contact with a riser's face from the side beyond what the steep segment gives.
+ *
+ * Following the ground (wbc_ground_follow_targets, wbc_ground_set_follow of include_ext/wbc_ground_follow.h; this project's definition).  The planners' 54 target rows
+ * (layout: wbc.h) are about the plane z = 0.  The follow law rewrites an instance's rows for the terrain it stands on, from its
+ * profile and its terrain_scale.  H(x, y) and g(x, y) are the scaled height and the scaled slope of the piece under (x, y), with the
+ * half-open pieces above; s(x, y) = (x - x0) cos(yaw) + (y - y0) sin(yaw), and for a horizontal vector u, u_s = u_x cos(yaw) +
+ * u_y sin(yaw).  Modes: WBC_FOLLOW_OFF (nothing), WBC_FOLLOW_LIFT (heights only), WBC_FOLLOW_FIT (heights and the trunk's attitude).
+ *   Feet (LIFT and FIT).  Foot i with target position p_i, velocity pd_i, acceleration pdd_i, and H_i, g_i taken at (p_i,x, p_i,y):
+ *     p_i,z += H_i,   pd_i,z += g_i (pd_i)_s,   pdd_i,z += g_i (pdd_i)_s;   x and y are untouched.
+ *   A foot whose target x or y is not finite is left entirely as it is and takes no part in the fit (a contact foot's target rows
+ *   may hold anything -- wbc.h -- and following must not turn such an instance into a status 2).
+ *   The fit, over the usable feet: s_m and H_m are the means of s_i and H_i, and
+ *     b = sum (s_i - s_m)(H_i - H_m) / sum (s_i - s_m)^2,
+ *   b = 0 where fewer than two feet are usable or the denominator is below 1e-12 m^2; with no usable foot H_m = H and s_m = s at the
+ *   body target's (x, y), and b = 0.
+ *   Body position (LIFT and FIT):  p_z += H_m + b (s(p_x, p_y) - s_m),   pd_z += b (pd)_s,   pdd_z += b (pdd)_s,   b taken as
+ *   constant in time.  On a plane this is the plane's height under the body; x and y are untouched, so the body stays over its feet.
+ *   Body attitude (FIT only).  R_fit is the rotation about the horizontal axis (-sin(yaw), cos(yaw), 0) by -atan(b): it takes world
+ *   z to the fitted plane's normal.  R' = R_fit Rz(yaw_b) Ry(pitch) Rx(roll), rpy' is read from R' (roll' = atan2(R'21, R'22),
+ *   pitch' = atan2(-R'20, sqrt(R'00^2 + R'10^2)), yaw' = atan2(R'10, R'00)), and rpyd' = E(rpy')^-1 R_fit E(rpy) rpyd, likewise rpydd,
+ *   where E(rpy) maps the rates of rpy to the angular velocity in the world; no E-dot term, as everywhere in this project.  Where
+ *   b = 0 (R_fit is the identity) or |cos pitch'| < 1e-9 the nine attitude rows are left as they are.
+ *   Untouched: an instance whose terrain_id >= count or whose terrain_scale is not finite keeps its targets bit for bit (the plant
+ *   reports it BAD anyway).  Non-finite values in rows that are read flow through the arithmetic and reach the tick, which answers
+ *   status 2 as it does today.
+ *   The limits: b and the foot slopes jump when a foothold crosses a knot; the attitude follows the fit of the four PLANNED footholds,
+ *   stance and swing alike; the planners do not re-plan footholds for the terrain; and the controllers' friction pyramids stay about
+ *   world z -- on a slope of grade gamma a controller mu of at most tan(atan(mu_p) - atan|gamma|) keeps an along-slope edge force
+ *   inside the plant's cone about the normal (terrain.py: pyramid_mu).
  *
  * Flags, per instance and per step, an int32 bit field:
  *   WBC_GROUND_SLIP  in some substep a loaded foot (f_n > 0) had |v_t| > v_stiction;
@@ -107,7 +134,8 @@ int wbc_ground_step(wbc_ground g, void* hip_stream, int n, int ld, double dt, do
  * does).  WBC_DEVICE_PTRS handles only; h and g on the same device.  The controller gets the schedule's contact_mask; the ground
  * decides what actually touches.  mu / mass_scale go to the controller, ground_mu / ground_mass_scale / ext_wrench to the plant.
  * Required: q, v, time, targets [54][ld], contact_mask [n], tau [12][ld].  The controller's statistics accumulate in h as they do in
- * wbc_rollout; on return targets / contact_mask / tau / metrics / status / force / contact / flags hold the last tick's values. */
+ * wbc_rollout; on return targets / contact_mask / tau / metrics / status / force / contact / flags hold the last tick's values.
+ * After wbc_ground_set_follow, with a terrain set, the follow law runs on the targets between the lookup and the tick. */
 int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stream, int steps, double dt, int n, int ld, double* q,
                        double* v, double* time, double* targets, uint8_t* contact_mask, const double* mu, const double* mass_scale,
                        const double* ground_mu, const double* ground_mass_scale, const double* ext_wrench, double* tau,
@@ -130,6 +158,12 @@ int wbc_ground_set_terrain(wbc_ground g, const wbc_terrain_profile* profiles, in
                            const double* terrain_scale);
 /* wbc_ground_kernel_info of the step kernel that runs while a terrain is set. */
 int wbc_ground_terrain_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads);
+
+/* ---- Following the ground (the law: the head of this file). */
+#define WBC_FOLLOW_OFF 0
+#define WBC_FOLLOW_LIFT 1
+#define WBC_FOLLOW_FIT 2
+/* The entry points: include_ext/wbc_ground_follow.h. */
 
 #ifdef __cplusplus
 }

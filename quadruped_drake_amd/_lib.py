@@ -117,9 +117,17 @@ PROTOTYPES = {
     "wbc_ground_terrain_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
 }
 SYMBOLS = list(PROTOTYPES)
-# what a library may lack: an older kernel build under A/B timing (WBC_HIP_LIB; tools/qt.py --lib) the statistics exchange, any library the terrain
+# the same for include_ext/wbc_ground_follow.h (the follow law of the ground plant), whose prototypes tests/test_follow_cpu.py lays
+# beside this table: the set that include/*.h declares is pinned as it stands
+EXT_PROTOTYPES = {
+    "wbc_ground_follow_targets": (_I, [_P, _P, _I, _I, _I, _P]),
+    "wbc_ground_set_follow": (_I, [_P, _I]),
+    "wbc_ground_follow_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
+}
+# what a library may lack: an older kernel build under A/B timing (WBC_HIP_LIB; tools/qt.py --lib) the statistics exchange and the
+# follow law, any library the terrain
 _MAY_LACK = ("wbc_terrain_check", "wbc_ground_set_terrain", "wbc_ground_terrain_kernel_info") + \
-    (("wbc_stats_pack", "wbc_stats_reduce") if "WBC_HIP_LIB" in os.environ else ())
+    (("wbc_stats_pack", "wbc_stats_reduce") + tuple(EXT_PROTOTYPES) if "WBC_HIP_LIB" in os.environ else ())
 
 
 class WbcError(RuntimeError):
@@ -144,7 +152,7 @@ def lib():
         except ImportError:
             pass
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXT_PROTOTYPES.items()):
             if not (name in _MAY_LACK and not hasattr(l, name)):
                 fn = getattr(l, name)
                 fn.restype, fn.argtypes = restype, argtypes

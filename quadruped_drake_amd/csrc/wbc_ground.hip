@@ -14,9 +14,11 @@
 
 #include "../../include/wbc.h"
 #include "../../include/wbc_ground.h"
+#include "../../include_ext/wbc_ground_follow.h"
 #include "wbc_model.hpp"
 #include "wbc_tick.hpp"
 #include "wbc_ground.hpp"
+#include "wbc_ground_follow.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
 
@@ -227,12 +229,21 @@ __global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_ground_terrain_forward_ke
   ground_body<false, true>(m, a, ta, lds);
 }
 
+// Targets that follow the terrain (wbc_ground_follow.hpp): one thread per robot, in place on targets [54][ld], the instance's rows
+// and its profile in registers before the first store.
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_ground_follow_kernel(int n, int ld, int mode, double* targets, TerrainArgs ta) {
+  const int i = blockIdx.x * wbc::QUAD_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  wbc::follow_instance(mode, ta.table, ta.count, ta.id, ta.scale, targets, (size_t)ld, (size_t)i);
+}
+
 struct wbc_ground_s {
   int device;
   wbc_ground_params params;
   wbc::ModelC* d_model;
   double* d_terrain;           // the packed table, TERRAIN_LDS_DOUBLES doubles, allocated by the first wbc_ground_set_terrain
   TerrainArgs terrain;         // count == 0: no terrain
+  int follow;                  // WBC_FOLLOW_*: what wbc_ground_rollout does to the targets between lookup and tick
 };
 
 namespace {
@@ -276,6 +287,16 @@ GroundArgs make_args(wbc_ground g, int n, int ld, int substeps, double dt, doubl
   a.fall_height = P.fall_height;
   return a;
 }
+
+// the follow kernel on targets [54][ld]; the caller has checked the arguments and that a terrain is set
+int launch_follow(wbc_ground g, hipStream_t s, int n, int ld, int mode, double* targets) {
+  hipLaunchKernelGGL(wbc_ground_follow_kernel, dim3((unsigned)((n + wbc::QUAD_BLOCK - 1) / wbc::QUAD_BLOCK)), dim3(wbc::QUAD_BLOCK), 0, s, n,
+                     ld, mode, targets, g->terrain);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+bool follow_mode_ok(int mode) { return mode == WBC_FOLLOW_OFF || mode == WBC_FOLLOW_LIFT || mode == WBC_FOLLOW_FIT; }
 
 void default_params(const wbc::ModelC& m, wbc_ground_params* out) {
   wbc::ground_default_law(m, &out->stiffness, &out->dissipation);
@@ -322,6 +343,7 @@ int wbc_ground_create(const wbc_model* model, const wbc_ground_params* params, i
   g->d_model = d;
   g->d_terrain = nullptr;
   g->terrain = TerrainArgs{};
+  g->follow = WBC_FOLLOW_OFF;
   *out = g;
   return 0;
 }
@@ -375,8 +397,32 @@ int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stre
   if (sub < 0) return sub;
   const GroundArgs a = make_args(g, n, ld, sub, dt, q, v, time, tau, ground_mu, ground_mass_scale, ext_wrench, nullptr, force, contact,
                                  flags, counts);
+  const bool follow = g->follow != WBC_FOLLOW_OFF && g->terrain.count > 0;   // otherwise: the launches of a rollout without it
   return wbc::plant_rollout("wbc_ground_rollout", h, traj, g->device, hip_stream, steps, n, ld, q, v, time, targets, contact_mask, mu,
-                            mass_scale, tau, metrics, status, [&] { return launch_ground(g, (hipStream_t)hip_stream, true, a); });
+                            mass_scale, tau, metrics, status, [&] { return launch_ground(g, (hipStream_t)hip_stream, true, a); },
+                            [&] { return follow ? launch_follow(g, (hipStream_t)hip_stream, n, ld, g->follow, targets) : 0; });
+}
+
+int wbc_ground_follow_targets(wbc_ground g, void* hip_stream, int n, int ld, int mode, double* targets) {
+  const int rc = wbc::plant_check_batch("wbc_ground_follow_targets", g, "ground", n, ld, targets != nullptr, "targets");
+  if (rc) return rc;
+  if (ld < n) return wbc::misuse("wbc_ground_follow_targets", "ld must be >= n");
+  if (!follow_mode_ok(mode)) return wbc::misuse("wbc_ground_follow_targets", "mode must be WBC_FOLLOW_OFF, WBC_FOLLOW_LIFT or WBC_FOLLOW_FIT");
+  if (n == 0 || mode == WBC_FOLLOW_OFF || g->terrain.count == 0) return 0;
+  WBC_ON_DEVICE(g->device, wbc::fail);
+  return launch_follow(g, (hipStream_t)hip_stream, n, ld, mode, targets);
+}
+
+int wbc_ground_set_follow(wbc_ground g, int mode) {
+  if (!g) return wbc::misuse("wbc_ground_set_follow: null ground handle");
+  if (!follow_mode_ok(mode)) return wbc::misuse("wbc_ground_set_follow", "mode must be WBC_FOLLOW_OFF, WBC_FOLLOW_LIFT or WBC_FOLLOW_FIT");
+  g->follow = mode;
+  return 0;
+}
+
+int wbc_ground_follow_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
+  if (!g) return wbc::misuse("wbc_ground_follow_kernel_info: null ground handle");
+  return WBC_PLANT_KERNEL_INFO(g->device, wbc_ground_follow_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
 }
 
 int wbc_ground_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {

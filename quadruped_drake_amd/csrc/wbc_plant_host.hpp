@@ -47,10 +47,14 @@ inline dim3 plant_grid(int n) { return dim3((unsigned)(((size_t)n * 4 + QUAD_BLO
 
 // `steps` x (target lookup at time -> controller tick -> plant step) on `device`, the plant step being `launch()`.  The batch
 // arguments were checked by the caller.  A host-pointer controller handle is refused before anything is launched.
-template <class Launch>
+// `between()` runs after the lookup and before the tick, on the targets the lookup wrote; by default it does nothing.
+struct NoRolloutHook {
+  int operator()() const { return 0; }
+};
+template <class Launch, class Between = NoRolloutHook>
 int plant_rollout(const char* fn, wbc_handle h, wbc_traj traj, int device, void* hip_stream, int steps, int n, int ld, double* q,
                   double* v, double* time, double* targets, uint8_t* contact_mask, const double* mu, const double* mass_scale,
-                  double* tau, double* metrics, int32_t* status, Launch launch) {
+                  double* tau, double* metrics, int32_t* status, Launch launch, Between between = Between()) {
   // wbc_integrate with n = 0 is an argument check only
   if (wbc_integrate(h, 0, 0, 0.0, nullptr, nullptr, nullptr)) return misuse(fn, "needs a WBC_DEVICE_PTRS controller handle");
   if (steps == 0 || n == 0) return 0;
@@ -59,6 +63,8 @@ int plant_rollout(const char* fn, wbc_handle h, wbc_traj traj, int device, void*
   WBC_ON_DEVICE(device, fail);
   for (int s = 0; s < steps; s++) {
     rc = wbc_traj_lookup(traj, hip_stream, n, ld, time, targets, contact_mask);
+    if (rc) return rc;
+    rc = between();
     if (rc) return rc;
     rc = wbc_step(h, n, ld, q, v, targets, contact_mask, mu, mass_scale, tau, metrics, status);
     if (rc) return rc;

@@ -9,7 +9,8 @@ lookup -> controller tick -> plant step on the device.  Torch tensors and torch'
 `GroundContactPlant` (include/wbc_ground.h) has a ground instead of held feet: a compliant half-space z = 0 whose force on each
 foot is an explicit function of the state, so feet lift off, land and slip and a robot that tips falls.  One `step` runs all
 explicit substeps of a control period in a single launch.  `set_terrain` replaces the plane by per-instance slopes, ramps and
-steps (terrain.py).  `closed_loop` takes either plant.
+steps (terrain.py), and `follow_targets` / `set_follow` make the planners' level-ground targets follow it.  `closed_loop` takes
+either plant.
 """
 import ctypes as C
 import math
@@ -20,6 +21,16 @@ from .controller import load_model
 
 PULL, CONE, CLIP, BAD = 1, 2, 4, 8
 SLIP, FELL = 1, 2   # GroundContactPlant's bits 0 and 1 (CLIP and BAD as above)
+FOLLOW_MODES = {"off": 0, "lift": 1, "fit": 2}   # WBC_FOLLOW_OFF / _LIFT / _FIT of include/wbc_ground.h
+
+
+def _follow_mode(mode):
+    """The WBC_FOLLOW_* number of a mode given by name or by number."""
+    if isinstance(mode, str):
+        if mode not in FOLLOW_MODES:
+            raise ValueError("follow mode %r: expected one of %s" % (mode, ", ".join(FOLLOW_MODES)))
+        return FOLLOW_MODES[mode]
+    return int(mode)
 
 
 _L = _lib.lib   # libwbc_hip.so, bound (the prototypes of every header: _lib.PROTOTYPES)
@@ -179,6 +190,27 @@ class GroundContactPlant(_Plant):
         arr = _terrain.c_array(profiles)
         _lib.check(self._L.wbc_ground_set_terrain(self._h, C.cast(arr, C.c_void_p), len(profiles), pid, psc))
         self._terrain = (profiles, terrain_id, terrain_scale, n)
+
+    def follow_targets(self, targets, mode="fit"):
+        """Make targets [54, N] follow the terrain set on this plant, in place (include/wbc_ground.h, "Following the ground"):
+        "lift" raises every foot target onto the surface under it and the body target onto the line fitted through the four planned
+        footholds; "fit" also turns the body's attitude with that line; "off" does nothing.  Without a terrain nothing is launched.
+        Asynchronous on torch's current stream.  -> targets"""
+        import torch
+        n = int(targets.shape[1])
+        self._check_terrain_n(n)
+        pt = _dev_ptr(targets, 54, n, torch.float64, "targets", self.device)
+        _lib.check(self._L.wbc_ground_follow_targets(self._h, self._stream(), n, n, _follow_mode(mode), pt))
+        return targets
+
+    def set_follow(self, mode):
+        """What closed_loop does between the target lookup and the tick on this plant: "off" (the default), "lift" or "fit", as
+        follow_targets.  With "off", or without a terrain, closed_loop launches what it launches without this call."""
+        _lib.check(self._L.wbc_ground_set_follow(self._h, _follow_mode(mode)))
+
+    def follow_kernel_info(self):
+        """kernel_info() of the kernel behind follow_targets."""
+        return self._kernel_info(self._L.wbc_ground_follow_kernel_info)
 
     def _check_terrain_n(self, n):
         if self._terrain is not None and self._terrain[3] is not None and self._terrain[3] < n:

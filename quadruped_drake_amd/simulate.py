@@ -14,7 +14,10 @@ controllers, not a physics engine.  No visualiser, no LCM.
 `--plant` chooses what the torques act on: `plan` (the default, the above), `rigid` (plant.RigidContactPlant: stance feet held,
 PULL / CONE reported) or `ground` (plant.GroundContactPlant: a compliant ground on which feet lift, land and slip and a robot
 can fall).  `--terrain NAME[:PARAM]` (with `--plant ground` only; terrain.SPECS) puts a slope, a ramp step, stairs or a ridge
-under the feet; the controllers still assume a level ground."""
+under the feet.  `--follow lift|fit` (with `--terrain` only; default `off`) makes the planner's level-ground targets follow that ground
+between the lookup and the tick: `lift` raises the foot and trunk heights, `fit` also turns the trunk's attitude with the line
+fitted through the planned footholds (include/wbc_ground.h).  The footholds are not re-planned and the controllers' friction pyramids
+stay about world z."""
 import argparse
 import json
 import sys
@@ -40,6 +43,8 @@ def parse(argv=None):
     ap.add_argument("--plant", default="plan", choices=("plan", "rigid", "ground"),
                     help="what the torques act on: the controller's own plan, the rigid-contact plant or the compliant-ground plant")
     ap.add_argument("--terrain", default=None, help="--plant ground only: NAME[:PARAM], e.g. slope:0.2 (flat, slope, ramp_step, stairs, ridge)")
+    ap.add_argument("--follow", default="off", choices=("off", "lift", "fit"),
+                    help="--terrain only: make the targets follow the ground (lift: heights; fit: heights and the trunk's attitude)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
@@ -55,6 +60,8 @@ def parse(argv=None):
             terrain.from_spec(a.terrain)
         except ValueError as e:
             ap.error(str(e))
+    if a.follow != "off" and a.terrain is None:
+        ap.error("--follow needs --terrain")
     if a.n < 1 or a.sim_time <= 0 or a.dt <= 0 or a.log_every < 1:
         ap.error("--n, --sim-time, --dt and --log-every must be positive")
     return a
@@ -90,6 +97,7 @@ def run(a):
                 from . import terrain
                 prof = terrain.from_spec(a.terrain)
                 plant.set_terrain([prof])
+                plant.set_follow(a.follow)
                 quat, pos = terrain.stance_pose(prof, 0.0, 0.0, float(q0[6, 0]))     # square on the ground under the start
                 q0[0:4] = quat[:, None]; q0[4:7] = pos[:, None]
         counts = torch.zeros((4, a.n), dtype=torch.int32, device=dev)
@@ -133,7 +141,7 @@ def main(argv=None):
     if a.plant != "plan":
         extra = {"plant": a.plant, "terrain": a.terrain, "plant_flags": r["plant_flags"]}
         if a.plant == "ground":
-            extra.update(FELL=r["plant_flags"]["fell"], SLIP=r["plant_flags"]["slip"])
+            extra.update(follow=a.follow, FELL=r["plant_flags"]["fell"], SLIP=r["plant_flags"]["slip"])
     print(json.dumps({"control": a.control, "planner": a.planner, "scenario": a.scenario if a.planner == "basic" else a.messages,
                       "n": a.n, "sim_time": a.sim_time, "dt": a.dt, "ticks": r["ticks"], "status_nonzero": r["status_nonzero"],
                       "ticks_per_second": r["ticks_per_second"], "active_set_iterations_mean": r["iters_mean"],

@@ -138,6 +138,13 @@ def from_spec(spec):
     return ridge(0.3, 0.5, 0.5, 0.1 if x is None else x)
 
 
+def pyramid_mu(mu_p, grade):
+    """tan(atan(mu_p) - atan|grade|): the largest controller `mu` whose friction pyramid about world z keeps an along-slope edge
+    force inside the plant's cone of friction mu_p about the normal of a slope of `grade` (the followed targets tilt the trunk,
+    the pyramids stay about z).  <= 0 where the slope is steeper than the cone: no force along world z stays inside it."""
+    return math.tan(math.atan(mu_p) - math.atan(abs(grade)))
+
+
 def stance_pose(profile, x, y, height, scale=1.0):
     """Quaternion (w, x, y, z) and position of a trunk standing square on the terrain above the surface point under (x, y): its
     z axis along the local normal, its origin `height` along the normal above the surface."""

@@ -2,13 +2,15 @@
 // Instantiates the compliant-ground plant math (quadruped_drake_amd/csrc/wbc_ground.hpp) on the host with `double`: the phases the
 // device kernel runs on the four lanes of a quad, here one leg after the other, with the quad sums as plain sums in the kernel's
 // order ((leg0 + leg1) + (leg2 + leg3)).  Both instantiations of the force law: the flat one (host_ground_batch) and the TERRAIN
-// one (host_terrain_batch), whose packed table -- staged in LDS by the device kernels -- lives in plain memory here.
-// tests/host_ground.py and tests/host_terrain.py load it; the shipped library never calls it.
+// one (host_terrain_batch), whose packed table -- staged in LDS by the device kernels -- lives in plain memory here; and the law
+// that makes the targets follow the terrain (host_follow_batch, wbc_ground_follow.hpp).
+// tests/host_ground.py, tests/host_terrain.py and tests/host_follow.py load it; the shipped library never calls it.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
 #include "../include/wbc_ground.h"
 #include "../quadruped_drake_amd/csrc/wbc_ground.hpp"
+#include "../quadruped_drake_amd/csrc/wbc_ground_follow.hpp"
 #include "host_batch.hpp"
 
 using namespace wbc;
@@ -141,6 +143,24 @@ int host_terrain_batch(const double* flat215, const int* q_perm, const int* act_
       ground_one<false>(m, P, i, (size_t)ld, step, substeps, dt, q, v, time, tau, mu, mass_scale, ext_wrench, vdot, force, contact, flags, counts);
   }
   return substeps;
+}
+
+// wbc_ground_follow_targets on the host: follow_instance of wbc_ground_follow.hpp, one instance after the other, in place on
+// targets [54][ld], with the terrain as wbc_ground_set_terrain takes it (host pointers).  No terrain, mode 0 or n = 0: nothing.
+// Returns 0, -2 on a malformed terrain, -3 on a mode outside 0 .. 2.
+int host_follow_batch(const wbc_terrain_profile* profiles, int count, const uint8_t* terrain_id, const double* terrain_scale, int n,
+                      int ld, int mode, double* targets) {
+  if (mode != FOLLOW_OFF && mode != FOLLOW_LIFT && mode != FOLLOW_FIT) return -3;
+  if (!profiles || count == 0 || mode == FOLLOW_OFF) return 0;
+  if (count < 1 || count > TERRAIN_MAX_PROFILES) return -2;
+  double table[TERRAIN_MAX_PROFILES * TERRAIN_STRIDE];
+  for (int p = 0; p < count; p++) {
+    const wbc_terrain_profile& t = profiles[p];
+    if (terrain_profile_error(t.nk, t.x0, t.y0, t.yaw, t.s, t.h)) return -2;
+    terrain_pack(t.nk, t.x0, t.y0, t.yaw, t.s, t.h, table + p * TERRAIN_STRIDE);
+  }
+  for (int i = 0; i < n; i++) follow_instance(mode, table, count, terrain_id, terrain_scale, targets, (size_t)ld, (size_t)i);
+  return 0;
 }
 
 // host_terrain_batch without a terrain
