@@ -55,6 +55,15 @@ class WbcTerrainProfile(C.Structure):
                 ("h", C.c_double * 8)]
 
 
+class WbcGaitStride(C.Structure):
+    _fields_ = [("nphase", C.c_int), ("duration", C.c_double * 8), ("contact", C.c_uint8 * 8)]
+
+
+class WbcGaitParams(C.Structure):
+    _fields_ = [("stance", (C.c_double * 2) * 4), ("height", C.c_double), ("swing_height", C.c_double), ("ramp_time", C.c_double),
+                ("wait_time", C.c_double)]
+
+
 _P, _I, _D = C.c_void_p, C.c_int, C.c_double
 _IP, _FP, _HP = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_void_p)
 _MODEL, _PARAMS, _STATS = C.POINTER(WbcModel), C.POINTER(WbcParams), C.POINTER(WbcStats)
@@ -124,10 +133,22 @@ EXT_PROTOTYPES = {
     "wbc_ground_set_follow": (_I, [_P, _I]),
     "wbc_ground_follow_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
 }
-# what a library may lack: an older kernel build under A/B timing (WBC_HIP_LIB; tools/qt.py --lib) the statistics exchange and the
-# follow law, any library the terrain
+# and for include_gait/wbc_gait.h (the gait planner), held to its header by tests/test_gait_cpu.py
+_GAITP, _GAITS = C.POINTER(WbcGaitParams), C.POINTER(WbcGaitStride)
+GAIT_PROTOTYPES = {
+    "wbc_gait_check": (_I, [_GAITP, _GAITS, _I]),
+    "wbc_gait_create": (_I, [_GAITP, _GAITS, _I, _I, _HP]),
+    "wbc_gait_destroy": (_I, [_P]),
+    "wbc_gait_set_commands": (_I, [_P, _P, _P, _P, _P]),
+    "wbc_gait_targets": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "wbc_gait_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
+    "wbc_ground_set_gait": (_I, [_P, _P]),
+    "wbc_plant_set_gait": (_I, [_P, _P]),
+}
+# what a library may lack: an older kernel build under A/B timing (WBC_HIP_LIB; tools/qt.py --lib) the statistics exchange, the
+# follow law and the gait planner, any library the terrain
 _MAY_LACK = ("wbc_terrain_check", "wbc_ground_set_terrain", "wbc_ground_terrain_kernel_info") + \
-    (("wbc_stats_pack", "wbc_stats_reduce") + tuple(EXT_PROTOTYPES) if "WBC_HIP_LIB" in os.environ else ())
+    (("wbc_stats_pack", "wbc_stats_reduce") + tuple(EXT_PROTOTYPES) + tuple(GAIT_PROTOTYPES) if "WBC_HIP_LIB" in os.environ else ())
 
 
 class WbcError(RuntimeError):
@@ -152,7 +173,7 @@ def lib():
         except ImportError:
             pass
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXT_PROTOTYPES.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXT_PROTOTYPES.items()) + list(GAIT_PROTOTYPES.items()):
             if not (name in _MAY_LACK and not hasattr(l, name)):
                 fn = getattr(l, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -1,0 +1,149 @@
+// wbc_gait.hip -- the gait planner (include_gait/wbc_gait.h): kernel and C ABI.
+//
+// Mapping of the plant kernels (wbc_quad.hpp): a quad of lanes per robot, one foot per lane, 16 robots per wavefront.  Every lane
+// loads its robot's nine inputs, the clock (stride, phase, mask) is replicated on the quad -- the same instructions on the same bits
+// -- and each lane evaluates its own foot's two footholds and the body's pose: three pose evaluations, two sincos each, which is the
+// kernel's latency chain.  Lane l stores its foot's nine rows; lane 0 also the 18 body rows and the mask.  The packed table
+// (wbc_gait.hpp) is staged in LDS once per block; every load is issued before the first store; nothing is read twice.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/wbc.h"
+#include "../../include_gait/wbc_gait.h"
+#include "wbc_gait.hpp"
+#include "wbc_quad.hpp"
+#include "wbc_plant_host.hpp"
+
+namespace {
+
+struct GaitArgs {
+  int n, ld, count;
+  const double* table;   // GAIT_HEAD + count * GAIT_STRIDE doubles
+  const double* time;
+  const double* cmd;
+  const uint8_t* gait_id;
+  const double* scale;
+  const double* start;
+  double* targets;
+  uint8_t* mask;
+};
+
+}  // namespace
+
+// stable kernel name (rocprofv3 --kernel-trace)
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_targets_kernel(GaitArgs a) {
+  using namespace wbc;
+  __shared__ double lds[GAIT_TABLE_DOUBLES];
+  const int words = GAIT_HEAD + a.count * GAIT_STRIDE;   // count <= WBC_GAIT_MAX_STRIDES: checked by wbc_gait_create
+  for (int k = threadIdx.x; k < words; k += QUAD_BLOCK) lds[k] = a.table[k];
+  const int t = blockIdx.x * QUAD_BLOCK + threadIdx.x;
+  const int l = t & 3;
+  const int r = t >> 2;
+  const bool live = r < a.n;
+  const size_t i = (size_t)(live ? r : a.n - 1);   // quads past the batch compute on its last robot and store nothing
+  const size_t ld = (size_t)a.ld;
+  const GaitIn in = gait_load(a.time, a.cmd, a.gait_id, a.scale, a.start, ld, i);
+  __syncthreads();
+  const GaitClock c = gait_clock(lds, a.count, in);
+  double b[18], f[9];
+  gait_foot(lds, in, c, l, f);
+  gait_body(lds, in, c, b);
+  if (!live) return;
+  double* out = a.targets + i;
+#pragma unroll
+  for (int k = 0; k < 9; k++) out[(size_t)(18 + 9 * l + k) * ld] = f[k];
+  if (l == 0) {
+#pragma unroll
+    for (int k = 0; k < 18; k++) out[(size_t)k * ld] = b[k];
+    a.mask[i] = (uint8_t)c.mask;
+  }
+}
+
+struct wbc_gait_s {
+  int device, count;
+  double table[wbc::GAIT_TABLE_DOUBLES];
+  double* d_table;       // allocated and filled by the first wbc_gait_set_commands
+  const double* cmd;     // nullptr: no wbc_gait_set_commands yet
+  const uint8_t* gait_id;
+  const double* scale;
+  const double* start;
+};
+
+extern "C" {
+
+int wbc_gait_check(const wbc_gait_params* params, const wbc_gait_stride* strides, int count) {
+  const char* what = wbc::gait_error(params, strides, count);
+  return what ? wbc::misuse("wbc_gait_check", what) : 0;
+}
+
+int wbc_gait_create(const wbc_gait_params* params, const wbc_gait_stride* strides, int count, int device, wbc_gait* out) {
+  static_assert(WBC_GAIT_MAX_PHASES == 8 && WBC_GAIT_MAX_STRIDES == 16, "the packed table's layout");
+  if (!out) return wbc::misuse("wbc_gait_create: null argument");
+  const char* what = wbc::gait_error(params, strides, count);
+  if (what) return wbc::misuse("wbc_gait_create", what);
+  if (device < 0) return wbc::misuse("wbc_gait_create: device must be >= 0");
+  wbc_gait g = new wbc_gait_s();
+  g->device = device;
+  g->count = count;
+  wbc::gait_pack(params, strides, count, g->table);
+  g->d_table = nullptr;
+  g->cmd = nullptr; g->gait_id = nullptr; g->scale = nullptr; g->start = nullptr;
+  *out = g;
+  return 0;
+}
+
+int wbc_gait_destroy(wbc_gait g) {
+  if (!g) return 0;
+  if (g->d_table) {
+    wbc::DeviceGuard device_guard_(g->device);
+    (void)hipDeviceSynchronize();   // a launch still reading the table
+    (void)hipFree(g->d_table);
+  }
+  delete g;
+  return 0;
+}
+
+int wbc_gait_set_commands(wbc_gait g, const double* cmd, const uint8_t* gait_id, const double* stride_scale, const double* start) {
+  if (!g) return wbc::misuse("wbc_gait_set_commands: null gait handle");
+  if (!cmd) return wbc::misuse("wbc_gait_set_commands: cmd is required");
+  if (!g->d_table) {
+    WBC_ON_DEVICE(g->device, wbc::fail);
+    const size_t bytes = (size_t)(wbc::GAIT_HEAD + g->count * wbc::GAIT_STRIDE) * sizeof(double);
+    double* d = nullptr;
+    HIP_TRY(hipMalloc(&d, bytes));
+    const hipError_t e = hipMemcpy(d, g->table, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      return wbc::fail("hipMemcpy(gait table)", e);
+    }
+    g->d_table = d;
+  }
+  g->cmd = cmd; g->gait_id = gait_id; g->scale = stride_scale; g->start = start;
+  return 0;
+}
+
+int wbc_gait_targets(wbc_gait g, void* hip_stream, int n, int ld, const double* time, double* targets, uint8_t* contact_mask) {
+  const int rc = wbc::plant_check_batch("wbc_gait_targets", g, "gait", n, ld, time && targets && contact_mask, "time, targets and contact_mask");
+  if (rc) return rc;
+  if (!g->cmd || !g->d_table) return wbc::misuse("wbc_gait_targets: wbc_gait_set_commands has not been called on this handle");
+  if (n == 0) return 0;
+  WBC_ON_DEVICE(g->device, wbc::fail);
+  GaitArgs a;
+  a.n = n; a.ld = ld; a.count = g->count; a.table = g->d_table; a.time = time; a.cmd = g->cmd; a.gait_id = g->gait_id;
+  a.scale = g->scale; a.start = g->start; a.targets = targets; a.mask = contact_mask;
+  hipLaunchKernelGGL(wbc_gait_targets_kernel, wbc::plant_grid(n), dim3(wbc::QUAD_BLOCK), 0, (hipStream_t)hip_stream, a);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// internal (not in include_gait/wbc_gait.h): the handle's device, for the plants' wbc_*_set_gait
+int wbc_gait_device_(wbc_gait g) { return g->device; }
+
+int wbc_gait_kernel_info(wbc_gait g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
+  if (!g) return wbc::misuse("wbc_gait_kernel_info: null gait handle");
+  return WBC_PLANT_KERNEL_INFO(g->device, wbc_gait_targets_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
+}
+
+}  // extern "C"

@@ -1,0 +1,255 @@
+// wbc_gait.hpp -- the gait planner's law (include_gait/wbc_gait.h, "The law"; product code): its one text, instantiated by
+// wbc_gait_targets_kernel (wbc_gait.hip, a quad of lanes per robot, one foot per lane) and by tools/host_gait.cpp.
+//
+// The host packs the parameters and every stride into one table of doubles (gait_pack): per (foot, phase) the bounds of the run the
+// phase lies in, relative to the start of the stride in progress, and for a swing run the bounds of the stance runs before and after
+// it -- so the device searches for no run and divides only where the law does.  The phase is picked by seven compares, a run's
+// six numbers by one indexed read of the table (LDS on the device): no indexed private array, hence no scratch.
+//
+//   table[0 .. 7]   stance[4][2]      table[8 .. 11]  height, swing_height, ramp_time, wait_time
+//   stride p at table + GAIT_HEAD + p * GAIT_STRIDE:
+//     [0 .. 6]  B_1 .. B_7, +inf from B_nphase on     [7] B_nphase     [8] the masks, phase j in bits 4j .. 4j+3     [9 .. 11] unused
+//     [12 + 6 (8 f + j) ..]  a, b of foot f's run around phase j; pa, pb and na, nb of the stance runs before and after it when it is
+//                            a swing run, a, b twice more when it is a stance run; a foot always in contact: -inf everywhere
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include_gait/wbc_gait.h"
+#include "wbc_tick.hpp"
+
+// the clock's arithmetic is rounded operation by operation on every instantiation (the header fixes k, r and the run times)
+#if defined(__clang__)
+#define WBC_GAIT_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define WBC_GAIT_NO_CONTRACT
+#endif
+#if defined(__HIPCC__)
+#define WBC_GAIT_UNROLL _Pragma("unroll")
+#else
+#define WBC_GAIT_UNROLL
+#endif
+
+namespace wbc {
+
+constexpr int GAIT_HEAD = 12;
+constexpr int GAIT_STRIDE = 12 + 6 * 8 * 4;                                      // 204 doubles
+constexpr int GAIT_TABLE_DOUBLES = GAIT_HEAD + WBC_GAIT_MAX_STRIDES * GAIT_STRIDE;   // 3276 doubles, 26208 B
+constexpr double GAIT_SINC_SMALL = 1e-4;
+
+// ---------------------------------------------------------------- host: checks and the packed table
+// what is wrong with the arguments of wbc_gait_check, or nullptr
+inline const char* gait_error(const wbc_gait_params* P, const wbc_gait_stride* S, int count) {
+  if (!P || !S) return "null params or strides";
+  if (count < 1 || count > WBC_GAIT_MAX_STRIDES) return "count must be 1 .. WBC_GAIT_MAX_STRIDES (16)";
+  const double* p = &P->stance[0][0];
+  for (int k = 0; k < 8; k++)
+    if (not_finite(p[k])) return "stance must be finite";
+  if (not_finite(P->height) || not_finite(P->swing_height) || not_finite(P->wait_time)) return "height, swing_height and wait_time must be finite";
+  if (!(P->ramp_time >= 0.0) || not_finite(P->ramp_time)) return "ramp_time must be non-negative and finite";
+  for (int s = 0; s < count; s++) {
+    const wbc_gait_stride& g = S[s];
+    if (g.nphase < 1 || g.nphase > WBC_GAIT_MAX_PHASES) return "nphase must be 1 .. WBC_GAIT_MAX_PHASES (8)";
+    unsigned any = 0;
+    for (int j = 0; j < g.nphase; j++) {
+      if (!(g.duration[j] > 0.0) || not_finite(g.duration[j])) return "every duration must be positive and finite";
+      if (g.contact[j] > 0xF) return "a contact mask has bits above 0xF";
+      any |= g.contact[j];
+    }
+    if (any != 0xF) return "every foot must be in contact in at least one phase";
+  }
+  return nullptr;
+}
+
+// table <- the parameters and `count` checked strides
+inline void gait_pack(const wbc_gait_params* P, const wbc_gait_stride* S, int count, double* table) {
+  for (int k = 0; k < 8; k++) table[k] = (&P->stance[0][0])[k];
+  table[8] = P->height; table[9] = P->swing_height; table[10] = P->ramp_time; table[11] = P->wait_time;
+  for (int s = 0; s < count; s++) {
+    const wbc_gait_stride& g = S[s];
+    double* t = table + GAIT_HEAD + s * GAIT_STRIDE;
+    const int n = g.nphase;
+    double B[WBC_GAIT_MAX_PHASES + 1];
+    B[0] = 0.0;
+    for (int j = 0; j < n; j++) B[j + 1] = B[j] + g.duration[j];
+    // the time of boundary i, any integer: B_(i mod n) + floor(i / n) B_n
+    auto at = [&](int i) {
+      int m = 0;
+      while (i < 0) { i += n; m--; }
+      while (i >= n) { i -= n; m++; }
+      return B[i] + (double)m * B[n];
+    };
+    double masks = 0.0, w = 1.0;
+    for (int j = 0; j < 8; j++) {
+      if (j < 7) t[j] = (j + 1 < n) ? B[j + 1] : INFINITY;
+      if (j < n) masks += w * (double)g.contact[j];
+      w *= 16.0;
+    }
+    t[7] = B[n]; t[8] = masks; t[9] = t[10] = t[11] = 0.0;
+    for (int f = 0; f < 4; f++) {
+      auto bit = [&](int i) { return (g.contact[((i % n) + n) % n] >> f) & 1; };
+      bool always = true;
+      for (int j = 0; j < n; j++) always &= bit(j) == 1;
+      for (int j = 0; j < 8; j++) {
+        double* e = t + 12 + 6 * (8 * f + j);
+        if (j >= n || always) {
+          for (int k = 0; k < 6; k++) e[k] = (j < n) ? -INFINITY : 0.0;
+          continue;
+        }
+        int lo = j, hi = j + 1;                           // the run is the phases lo .. hi-1: boundaries lo and hi
+        while (bit(lo - 1) == bit(j)) lo--;
+        while (bit(hi) == bit(j)) hi++;
+        e[0] = at(lo); e[1] = at(hi);
+        if (bit(j)) {
+          e[2] = e[0]; e[3] = e[1]; e[4] = e[0]; e[5] = e[1];
+        } else {
+          int plo = lo, nhi = hi + 1;                     // the stance runs plo .. lo and hi .. nhi
+          while (bit(plo - 1) == 1) plo--;
+          while (bit(nhi) == 1) nhi++;
+          e[2] = at(plo); e[3] = at(lo); e[4] = at(hi); e[5] = at(nhi);
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- host and device: one instance
+struct GaitIn {        // what an instance brings
+  double time, cx, cy, w, s, x0, y0, psi0;
+  int id;
+};
+struct GaitClock {     // where an instance is in its stride
+  bool bad, pre;       // malformed; tau < 0 (standing)
+  double tau, s, k, kT;   // kT: the start of the stride in progress
+  int phase;
+  unsigned mask;
+  const double* stride;
+};
+
+// theta, theta', theta'' at t >= 0
+WBC_HD void gait_theta(double ramp, double t, double& th, double& thd, double& thdd) {
+  const double x = t / ramp, y = 1.0 - x;               // ramp = 0: not used below
+  const bool in = t < ramp;
+  th = in ? ramp * ((x * x) * (x * x) * (2.5 + x * (x - 3.0))) : t - 0.5 * ramp;
+  thd = in ? (x * x) * x * (10.0 + x * (6.0 * x - 15.0)) : 1.0;
+  thdd = in ? 30.0 * (x * x) * (y * y) / ramp : 0.0;
+}
+
+// the body's (x, y) and the cosine and sine of its yaw at path parameter th
+WBC_HD void gait_pose(const GaitIn& in, double th, double& x, double& y, double& cpsi, double& spsi) {
+  const double a = 0.5 * (in.w * th);
+  double sa, ca, sm, cm;
+  wbc_sincos(a, sa, ca);
+  wbc_sincos(in.psi0 + a, sm, cm);
+  const double sinc = fabs(a) < GAIT_SINC_SMALL ? 1.0 - a * a / 6.0 : sa / a;
+  const double g = th * sinc;
+  x = in.x0 + g * (cm * in.cx - sm * in.cy);
+  y = in.y0 + g * (sm * in.cx + cm * in.cy);
+  cpsi = cm * ca - sm * sa;
+  spsi = sm * ca + cm * sa;
+}
+
+// the clock of one instance; `count` strides in `table`.  A malformed instance runs on stride 0 at scale 1 and is answered with NaN.
+WBC_HD GaitClock gait_clock(const double* table, int count, const GaitIn& in) {
+  WBC_GAIT_NO_CONTRACT
+  GaitClock c;
+  c.bad = (in.id >= count) | !(in.s > 0.0) | not_finite(in.s) | not_finite(in.time) | not_finite(in.cx) | not_finite(in.cy) |
+          not_finite(in.w) | not_finite(in.x0) | not_finite(in.y0) | not_finite(in.psi0);
+  c.stride = table + GAIT_HEAD + (c.bad ? 0 : in.id) * GAIT_STRIDE;
+  c.s = c.bad ? 1.0 : in.s;
+  c.tau = in.time - table[11];
+  c.pre = c.tau < 0.0;
+  const double T = c.s * c.stride[7];
+  double k = floor(c.tau / T);
+  k = (k * T > c.tau) ? k - 1.0 : k;
+  k = ((k + 1.0) * T <= c.tau) ? k + 1.0 : k;
+  c.k = k;
+  c.kT = k * T;
+  const double r = c.tau - c.kT;
+  int j = 0;
+  WBC_GAIT_UNROLL
+  for (int m = 0; m < 7; m++) j += (r >= c.s * c.stride[m]) ? 1 : 0;
+  c.phase = j;
+  c.mask = (c.bad | c.pre) ? 0xFu : (((unsigned)c.stride[8] >> (4 * j)) & 0xFu);
+  return c;
+}
+
+// the 18 body rows
+WBC_HD void gait_body(const double* table, const GaitIn& in, const GaitClock& c, double* b) {
+  double th, thd, thdd, x, y, cp, sp;
+  gait_theta(table[10], c.pre ? 0.0 : c.tau, th, thd, thdd);
+  th = c.pre ? 0.0 : th; thd = c.pre ? 0.0 : thd; thdd = c.pre ? 0.0 : thdd;
+  gait_pose(in, th, x, y, cp, sp);
+  const double vx = cp * in.cx - sp * in.cy, vy = sp * in.cx + cp * in.cy;   // Rz(psi) c
+  const double cen = thd * thd * in.w;
+  const double nan = __builtin_nan("");
+  b[0] = x; b[1] = y; b[2] = table[8];
+  b[3] = thd * vx; b[4] = thd * vy; b[5] = 0.0;
+  b[6] = thdd * vx - cen * vy; b[7] = thdd * vy + cen * vx; b[8] = 0.0;
+  b[9] = 0.0; b[10] = 0.0; b[11] = in.psi0 + in.w * th;
+  b[12] = 0.0; b[13] = 0.0; b[14] = in.w * thd;
+  b[15] = 0.0; b[16] = 0.0; b[17] = in.w * thdd;
+  WBC_GAIT_UNROLL
+  for (int r = 0; r < 18; r++) b[r] = c.bad ? nan : b[r];
+}
+
+// the 9 rows of foot f; run (optional, for the tests): the start a of the run the foot is in, and u = (tau - a) / D as the rows use it
+WBC_HD void gait_foot(const double* table, const GaitIn& in, const GaitClock& c, int f, double* o, double* run = nullptr) {
+  const double* e = c.stride + 12 + 6 * (8 * f + c.phase);
+  const double sx = table[2 * f], sy = table[2 * f + 1], ramp = table[10];
+  double a, b, pa, pb, na, nb;
+  {
+    WBC_GAIT_NO_CONTRACT
+    a = c.kT + c.s * e[0]; b = c.kT + c.s * e[1];
+    pa = c.kT + c.s * e[2]; pb = c.kT + c.s * e[3];
+    na = c.kT + c.s * e[4]; nb = c.kT + c.s * e[5];
+  }
+  const bool swing = !((c.mask >> f) & 1u);
+  // the two footholds: of the stance run before and after a swing run; a stance run's own, twice
+  double F[2][2];
+  WBC_GAIT_UNROLL
+  for (int h = 0; h < 2; h++) {
+    const double lo = h ? na : pa, hi = h ? nb : pb;
+    double th, thd, thdd, x, y, cp, sp;
+    gait_theta(ramp, fmax(0.5 * (lo + hi), 0.0), th, thd, thdd);
+    th = (c.pre | (lo <= 0.0)) ? 0.0 : th;
+    gait_pose(in, th, x, y, cp, sp);
+    F[h][0] = x + (cp * sx - sp * sy);
+    F[h][1] = y + (sp * sx + cp * sy);
+  }
+  const double D = b - a, u = (c.tau - a) / D, w = 1.0 - u, uw = u * w;
+  if (run) { run[0] = a; run[1] = u; }
+  const double sg = (u * u) * u * (10.0 + u * (6.0 * u - 15.0));
+  const double sgd = 30.0 * (uw * uw) / D, sgdd = 60.0 * uw * (1.0 - 2.0 * u) / (D * D);
+  const double hz = table[9] * 64.0;
+  const double z = hz * (uw * uw) * uw, zd = hz * 3.0 * (uw * uw) * (1.0 - 2.0 * u) / D;
+  const double zdd = hz * 6.0 * uw * (1.0 + 5.0 * u * (u - 1.0)) / (D * D);
+  const double dx = F[1][0] - F[0][0], dy = F[1][1] - F[0][1];
+  const double nan = __builtin_nan("");
+  o[0] = swing ? F[0][0] + dx * sg : F[0][0];
+  o[1] = swing ? F[0][1] + dy * sg : F[0][1];
+  o[2] = swing ? z : 0.0;
+  o[3] = swing ? dx * sgd : 0.0;
+  o[4] = swing ? dy * sgd : 0.0;
+  o[5] = swing ? zd : 0.0;
+  o[6] = swing ? dx * sgdd : 0.0;
+  o[7] = swing ? dy * sgdd : 0.0;
+  o[8] = swing ? zdd : 0.0;
+  WBC_GAIT_UNROLL
+  for (int r = 0; r < 9; r++) o[r] = c.bad ? nan : o[r];
+}
+
+// instance i of a batch: the inputs as wbc_gait_set_commands takes them (null optional pointers: their defaults)
+WBC_HD GaitIn gait_load(const double* time, const double* cmd, const uint8_t* gait_id, const double* stride_scale, const double* start,
+                        size_t ld, size_t i) {
+  GaitIn in;
+  in.time = time[i];
+  in.cx = cmd[i]; in.cy = cmd[ld + i]; in.w = cmd[2 * ld + i];
+  in.id = gait_id ? (int)gait_id[i] : 0;
+  in.s = stride_scale ? stride_scale[i] : 1.0;
+  in.x0 = start ? start[i] : 0.0; in.y0 = start ? start[ld + i] : 0.0; in.psi0 = start ? start[2 * ld + i] : 0.0;
+  return in;
+}
+
+}  // namespace wbc

@@ -15,12 +15,15 @@
 #include "../../include/wbc.h"
 #include "../../include/wbc_ground.h"
 #include "../../include_ext/wbc_ground_follow.h"
+#include "../../include_gait/wbc_gait.h"
 #include "wbc_model.hpp"
 #include "wbc_tick.hpp"
 #include "wbc_ground.hpp"
 #include "wbc_ground_follow.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
+
+extern "C" int wbc_gait_device_(wbc_gait g);   // wbc_gait.hip (internal): the device a gait handle was created for
 
 namespace {
 
@@ -244,6 +247,7 @@ struct wbc_ground_s {
   double* d_terrain;           // the packed table, TERRAIN_LDS_DOUBLES doubles, allocated by the first wbc_ground_set_terrain
   TerrainArgs terrain;         // count == 0: no terrain
   int follow;                  // WBC_FOLLOW_*: what wbc_ground_rollout does to the targets between lookup and tick
+  wbc_gait gait;               // not null: wbc_ground_rollout takes its targets from it, not from the trajectory
 };
 
 namespace {
@@ -344,6 +348,7 @@ int wbc_ground_create(const wbc_model* model, const wbc_ground_params* params, i
   g->d_terrain = nullptr;
   g->terrain = TerrainArgs{};
   g->follow = WBC_FOLLOW_OFF;
+  g->gait = nullptr;
   *out = g;
   return 0;
 }
@@ -390,7 +395,7 @@ int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stre
                        double* metrics, int32_t* status, double* force, uint8_t* contact, int32_t* flags, int32_t* counts) {
   const int rc = check_ground_args("wbc_ground_rollout", g, n, ld, q, v, tau);
   if (rc) return rc;
-  if (!h || !traj) return wbc::misuse("wbc_ground_rollout: null controller or trajectory handle");
+  if (!h || (!traj && !g->gait)) return wbc::misuse("wbc_ground_rollout: null controller or trajectory handle");
   if (steps < 0) return wbc::misuse("wbc_ground_rollout: steps must be >= 0");
   if (n > 0 && (!time || !targets || !contact_mask)) return wbc::misuse("wbc_ground_rollout: time, targets and contact_mask are required");
   const int sub = substeps_for("wbc_ground_rollout", g, dt);
@@ -398,9 +403,20 @@ int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stre
   const GroundArgs a = make_args(g, n, ld, sub, dt, q, v, time, tau, ground_mu, ground_mass_scale, ext_wrench, nullptr, force, contact,
                                  flags, counts);
   const bool follow = g->follow != WBC_FOLLOW_OFF && g->terrain.count > 0;   // otherwise: the launches of a rollout without it
+  // the tick's targets: the gait's while one is set, else the lookup in `traj` -- the launch a rollout without a gait issues
+  auto source = [&](wbc_traj tr, void* s, int n_, int ld_, const double* t, double* tg, uint8_t* m) {
+    return g->gait ? wbc_gait_targets(g->gait, s, n_, ld_, t, tg, m) : wbc_traj_lookup(tr, s, n_, ld_, t, tg, m);
+  };
   return wbc::plant_rollout("wbc_ground_rollout", h, traj, g->device, hip_stream, steps, n, ld, q, v, time, targets, contact_mask, mu,
                             mass_scale, tau, metrics, status, [&] { return launch_ground(g, (hipStream_t)hip_stream, true, a); },
-                            [&] { return follow ? launch_follow(g, (hipStream_t)hip_stream, n, ld, g->follow, targets) : 0; });
+                            [&] { return follow ? launch_follow(g, (hipStream_t)hip_stream, n, ld, g->follow, targets) : 0; }, source);
+}
+
+int wbc_ground_set_gait(wbc_ground g, wbc_gait gait) {
+  if (!g) return wbc::misuse("wbc_ground_set_gait: null ground handle");
+  if (gait && wbc_gait_device_(gait) != g->device) return wbc::misuse("wbc_ground_set_gait: the gait handle lives on another device than the plant");
+  g->gait = gait;
+  return 0;
 }
 
 int wbc_ground_follow_targets(wbc_ground g, void* hip_stream, int n, int ld, int mode, double* targets) {

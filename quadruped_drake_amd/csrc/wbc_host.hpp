@@ -1,5 +1,5 @@
-// wbc_host.hpp -- the host side that the four translation units of the C ABI share (wbc_kernels.hip, wbc_traj.hip, wbc_plant.hip,
-// wbc_ground.hip; internal, not installed): error reporting, the checks of a caller's model table and joint numbering, and the
+// wbc_host.hpp -- the host side that the five translation units of the C ABI share (wbc_kernels.hip, wbc_traj.hip, wbc_plant.hip,
+// wbc_ground.hip, wbc_gait.hip; internal, not installed): error reporting, the checks of a caller's model table and joint numbering, and the
 // answer of a *_kernel_info entry point.  Host code only: nothing here decides a device instruction.
 #pragma once
 #include <hip/hip_runtime.h>

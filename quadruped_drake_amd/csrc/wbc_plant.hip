@@ -12,11 +12,14 @@
 
 #include "../../include/wbc.h"
 #include "../../include/wbc_plant.h"
+#include "../../include_gait/wbc_gait.h"
 #include "wbc_model.hpp"
 #include "wbc_tick.hpp"
 #include "wbc_plant.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
+
+extern "C" int wbc_gait_device_(wbc_gait g);   // wbc_gait.hip (internal): the device a gait handle was created for
 
 namespace {
 
@@ -221,6 +224,7 @@ struct wbc_plant_s {
   int device;
   wbc_plant_params params;
   wbc::ModelC* d_model;
+  wbc_gait gait;   // not null: wbc_plant_rollout takes its targets from it, not from the trajectory
 };
 
 namespace {
@@ -277,6 +281,7 @@ int wbc_plant_create(const wbc_model* model, const wbc_plant_params* params, int
   p->device = device;
   p->params = P;
   p->d_model = d;
+  p->gait = nullptr;
   *out = p;
   return 0;
 }
@@ -320,12 +325,24 @@ int wbc_plant_rollout(wbc_handle h, wbc_plant p, wbc_traj traj, void* hip_stream
                       double* force, int32_t* flags, int32_t* counts) {
   const int rc = check_plant_args("wbc_plant_rollout", p, n, ld, q, v, tau, contact_mask);
   if (rc) return rc;
-  if (!h || !traj) return wbc::misuse("wbc_plant_rollout: null controller or trajectory handle");
+  if (!h || (!traj && !p->gait)) return wbc::misuse("wbc_plant_rollout: null controller or trajectory handle");
   if (steps < 0) return wbc::misuse("wbc_plant_rollout: steps must be >= 0");
   if (n > 0 && (!time || !targets)) return wbc::misuse("wbc_plant_rollout: time and targets are required");
   const PlantArgs a = make_args(p, n, ld, dt, q, v, time, tau, contact_mask, plant_mu, plant_mass_scale, nullptr, force, flags, counts);
+  // the tick's targets: the gait's while one is set, else the lookup in `traj` -- the launch a rollout without a gait issues
+  auto source = [&](wbc_traj tr, void* s, int n_, int ld_, const double* t, double* tg, uint8_t* m) {
+    return p->gait ? wbc_gait_targets(p->gait, s, n_, ld_, t, tg, m) : wbc_traj_lookup(tr, s, n_, ld_, t, tg, m);
+  };
   return wbc::plant_rollout("wbc_plant_rollout", h, traj, p->device, hip_stream, steps, n, ld, q, v, time, targets, contact_mask, mu,
-                            mass_scale, tau, metrics, status, [&] { return launch_plant(p, (hipStream_t)hip_stream, true, a); });
+                            mass_scale, tau, metrics, status, [&] { return launch_plant(p, (hipStream_t)hip_stream, true, a); },
+                            wbc::NoRolloutHook(), source);
+}
+
+int wbc_plant_set_gait(wbc_plant p, wbc_gait gait) {
+  if (!p) return wbc::misuse("wbc_plant_set_gait: null plant handle");
+  if (gait && wbc_gait_device_(gait) != p->device) return wbc::misuse("wbc_plant_set_gait: the gait handle lives on another device than the plant");
+  p->gait = gait;
+  return 0;
 }
 
 int wbc_plant_kernel_info(wbc_plant p, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {

@@ -48,13 +48,20 @@ inline dim3 plant_grid(int n) { return dim3((unsigned)(((size_t)n * 4 + QUAD_BLO
 // `steps` x (target lookup at time -> controller tick -> plant step) on `device`, the plant step being `launch()`.  The batch
 // arguments were checked by the caller.  A host-pointer controller handle is refused before anything is launched.
 // `between()` runs after the lookup and before the tick, on the targets the lookup wrote; by default it does nothing.
+// `source(traj, hip_stream, n, ld, time, targets, contact_mask)` writes a tick's targets and mask; by default it is the lookup in
+// `traj` (a gait set on the plant handle takes its place: include_gait/wbc_gait.h).
 struct NoRolloutHook {
   int operator()() const { return 0; }
 };
-template <class Launch, class Between = NoRolloutHook>
+struct TrajLookupSource {
+  int operator()(wbc_traj traj, void* hip_stream, int n, int ld, const double* time, double* targets, uint8_t* contact_mask) const {
+    return wbc_traj_lookup(traj, hip_stream, n, ld, time, targets, contact_mask);
+  }
+};
+template <class Launch, class Between = NoRolloutHook, class Source = TrajLookupSource>
 int plant_rollout(const char* fn, wbc_handle h, wbc_traj traj, int device, void* hip_stream, int steps, int n, int ld, double* q,
                   double* v, double* time, double* targets, uint8_t* contact_mask, const double* mu, const double* mass_scale,
-                  double* tau, double* metrics, int32_t* status, Launch launch, Between between = Between()) {
+                  double* tau, double* metrics, int32_t* status, Launch launch, Between between = Between(), Source source = Source()) {
   // wbc_integrate with n = 0 is an argument check only
   if (wbc_integrate(h, 0, 0, 0.0, nullptr, nullptr, nullptr)) return misuse(fn, "needs a WBC_DEVICE_PTRS controller handle");
   if (steps == 0 || n == 0) return 0;
@@ -62,7 +69,7 @@ int plant_rollout(const char* fn, wbc_handle h, wbc_traj traj, int device, void*
   if (rc) return rc;
   WBC_ON_DEVICE(device, fail);
   for (int s = 0; s < steps; s++) {
-    rc = wbc_traj_lookup(traj, hip_stream, n, ld, time, targets, contact_mask);
+    rc = source(traj, hip_stream, n, ld, time, targets, contact_mask);
     if (rc) return rc;
     rc = between();
     if (rc) return rc;

@@ -1,0 +1,149 @@
+"""Gait planner on the device (include_gait/wbc_gait.h): walking targets from a velocity command.
+
+The reference gets its walking `trunk_input` from TOWR, which is out of scope here.  As far as the controllers see it, that is a
+contact schedule, footholds, swing splines and a base motion.  The schedule is data -- TOWR's stride tables, restated in `STRIDES`
+-- and once the base follows a commanded velocity the rest has a closed form (the law: the head of include_gait/wbc_gait.h).
+`GaitPlanner` evaluates it per instance on the GPU: every robot of a batch has its own command (vx, vy, yaw rate), its own stride
+and its own stride period, and no table of samples.  `plant.closed_loop` takes a GaitPlanner where it takes a trajectory.
+Torch tensors and torch's current stream, as in controller.py and plant.py.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib, workloads
+
+FEET = ("LF", "RF", "LH", "RH")   # bit i of a contact mask (towr/include/towr/models/endeffector_mappings.h: enum QuadrupedIDs)
+# towr/src/quadruped_gait_generator.cc:50-70 names a contact state by two letters, hind legs then front legs: I none, P the left
+# one, b the right one, B both.
+_II, _PI, _bI, _IP, _Ib = 0b0000, 0b0100, 0b1000, 0b0001, 0b0010
+_Pb, _bP, _BI, _IB, _PP, _bb = 0b0110, 0b1001, 0b1100, 0b0011, 0b0101, 0b1010
+_Bb, _BP, _bB, _PB, _BB = 0b1110, 0b1101, 0b1011, 0b0111, 0b1111
+
+# name -> (durations [s], contact masks), one entry per phase: the strides of towr/src/quadruped_gait_generator.cc
+STRIDES = {
+    "stand": ((0.3,), (_BB,)),                                                                      # :113-126 GetStrideStand
+    "walk": ((0.3, 0.2, 0.3, 0.2, 0.3, 0.2, 0.3, 0.2), (_bB, _BB, _Bb, _BB, _PB, _BB, _BP, _BB)),   # :162-179 GetStrideWalk
+    "walk_overlap": ((0.25, 0.13, 0.25, 0.13, 0.25, 0.13, 0.25, 0.13),
+                     (_bB, _bb, _Bb, _Pb, _PB, _PP, _BP, _bP)),                                     # :181-204 GetStrideWalkOverlap
+    "trot": ((0.3, 0.2, 0.3, 0.2), (_bP, _BB, _Pb, _BB)),                                           # :206-221 GetStrideTrot
+    "trot_fly": ((0.4, 0.1, 0.4, 0.1), (_bP, _II, _Pb, _II)),                                       # :223-240 GetStrideTrotFly
+    "pace": ((0.3, 0.1, 0.3, 0.1), (_PP, _II, _bb, _II)),                                           # :257-273 GetStridePace
+    "bound": ((0.3, 0.1, 0.3, 0.1), (_BI, _II, _IB, _II)),                                          # :290-306 GetStrideBound
+    "pronk": ((0.3, 0.4, 0.3), (_BB, _II, _BB)),                                                    # :143-160 GetStridePronk
+    "gallop": ((0.2, 0.3, 0.2, 0.2, 0.2, 0.3, 0.2, 0.2), (_Bb, _BI, _BP, _bP, _bB, _IB, _PB, _Pb)),  # :323-345 GetStrideGallop
+    "limp": ((0.1, 0.2, 0.1, 0.1, 0.2, 0.1), (_Bb, _BB, _IP, _Bb, _BB, _IP)),                       # :347-366 GetStrideLimp
+}
+MAX_STRIDES, MAX_PHASES = 16, 8   # WBC_GAIT_MAX_STRIDES, WBC_GAIT_MAX_PHASES
+
+
+def stride(spec):
+    """(durations, masks) of a stride given by its name in STRIDES or as such a pair."""
+    if isinstance(spec, str):
+        if spec not in STRIDES:
+            raise ValueError("gait %r: expected one of %s" % (spec, ", ".join(STRIDES)))
+        spec = STRIDES[spec]
+    d, m = spec
+    d, m = [float(x) for x in d], [int(x) for x in m]
+    if len(d) != len(m) or not 1 <= len(d) <= MAX_PHASES:
+        raise ValueError("a stride is 1 .. %d phases, a duration and a contact mask each" % MAX_PHASES)
+    return d, m
+
+
+def c_strides(specs):
+    """The wbc_gait_stride array of a list of strides (names or (durations, masks) pairs)."""
+    specs = list(specs)
+    arr = (_lib.WbcGaitStride * max(len(specs), 1))()
+    for s, spec in zip(arr, specs):
+        d, m = stride(spec)
+        s.nphase = len(d)
+        for j in range(len(d)):
+            s.duration[j] = d[j]
+            s.contact[j] = m[j] & 0xFF
+    return arr
+
+
+def c_params(stance, height, swing_height, ramp_time, wait_time):
+    """The wbc_gait_params of stance [4, 2] (or [4, 3]: workloads.STAND_FEET) and the four scalars."""
+    p = _lib.WbcGaitParams()
+    st = np.asarray(stance, dtype=np.float64)
+    for f in range(4):
+        p.stance[f][0], p.stance[f][1] = float(st[f, 0]), float(st[f, 1])
+    p.height, p.swing_height, p.ramp_time, p.wait_time = float(height), float(swing_height), float(ramp_time), float(wait_time)
+    return p
+
+
+class GaitPlanner:
+    """The targets of N walking robots, each with its own command (include_gait/wbc_gait.h).
+
+    model: a name of workloads.STAND_FEET, which gives the nominal stance and height (or pass stance [4, 2] and height);
+    strides: up to 16 strides, names of STRIDES or (durations, masks) pairs; instance i walks strides[gait_id[i]].
+    swing_height [m]; ramp_time [s]: the body reaches its commanded velocity smoothly over this time, stepping in place at first;
+    wait_time [s]: standing targets before it, as the trajectories have it."""
+
+    def __init__(self, model="mini_cheetah", strides=("trot",), swing_height=0.05, ramp_time=0.5, wait_time=0.0, device=0, stance=None,
+                 height=None):
+        if stance is None or height is None:
+            if model not in workloads.STAND_FEET:
+                raise ValueError("GaitPlanner: no nominal stance for model %r; pass stance and height" % (model,))
+            stance = workloads.STAND_FEET[model] if stance is None else stance
+            height = workloads.NOMINAL_HEIGHT[model] if height is None else height
+        strides = [strides] if isinstance(strides, str) else list(strides)
+        self.strides = [stride(s) for s in strides]
+        self.params = c_params(stance, height, swing_height, ramp_time, wait_time)
+        self.device = int(device)
+        self._L = _lib.lib()
+        self._h = None
+        self._n = None
+        self._keep = None
+        h = C.c_void_p()
+        _lib.check(self._L.wbc_gait_create(C.byref(self.params), c_strides(self.strides), len(self.strides), self.device, C.byref(h)))
+        self._h = h
+
+    def set_commands(self, cmd, gait_id=None, stride_scale=None, start=None):
+        """cmd [3, N] float64 = (vx, vy, yaw rate), velocity in the heading frame; gait_id [N] uint8 (None: stride 0); stride_scale [N]
+        float64 (None: 1.0; the stride's durations times it); start [3, N] float64 = (x0, y0, yaw0) (None: 0).  The tensors live on
+        the planner's device and are kept alive here; rewriting them changes what the next targets() gives."""
+        import torch
+        if not (isinstance(cmd, torch.Tensor) and cmd.dim() == 2):
+            raise ValueError("cmd: expected a CUDA tensor of shape [3, N]")
+        n, d = int(cmd.shape[1]), self.device
+        pc = _lib.dev_ptr(cmd, 3, n, torch.float64, "cmd", d, "the planner")
+        pg = _lib.dev_ptr(gait_id, 0, n, torch.uint8, "gait_id", d, "the planner", True)
+        ps = _lib.dev_ptr(stride_scale, 0, n, torch.float64, "stride_scale", d, "the planner", True)
+        p0 = _lib.dev_ptr(start, 3, n, torch.float64, "start", d, "the planner", True)
+        _lib.check(self._L.wbc_gait_set_commands(self._h, pc, pg, ps, p0))
+        self._n, self._keep = n, (cmd, gait_id, stride_scale, start)
+
+    def targets(self, time, out=None):
+        """-> (targets [54, N] float64, contact_mask [N] uint8) at time [N] float64; out: such a pair to write into.  Asynchronous on
+        torch's current stream."""
+        import torch
+        if self._n is None:
+            raise ValueError("GaitPlanner.targets: set_commands first")
+        n, d = self._n, self.device
+        pt = _lib.dev_ptr(time, 0, n, torch.float64, "time", d, "the planner")
+        if out is None:
+            out = (torch.empty((54, n), dtype=torch.float64, device="cuda:%d" % d), torch.empty((n,), dtype=torch.uint8, device="cuda:%d" % d))
+        tg, mk = out
+        ptg = _lib.dev_ptr(tg, 54, n, torch.float64, "targets", d, "the planner")
+        pmk = _lib.dev_ptr(mk, 0, n, torch.uint8, "contact_mask", d, "the planner")
+        s = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
+        _lib.check(self._L.wbc_gait_targets(self._h, s, n, n, pt, ptg, pmk))
+        return tg, mk
+
+    def kernel_info(self):
+        """Registers, scratch bytes per lane, LDS bytes and threads per block of the gait kernel."""
+        return _lib.kernel_info(self._L.wbc_gait_kernel_info, self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.wbc_gait_destroy(self._h)
+            self._h = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

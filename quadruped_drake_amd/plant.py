@@ -12,6 +12,7 @@ explicit substeps of a control period in a single launch.  `set_terrain` replace
 steps (terrain.py), and `follow_targets` / `set_follow` make the planners' level-ground targets follow it.  `closed_loop` takes
 either plant.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -270,14 +271,32 @@ class GroundContactPlant(_Plant):
         return self._kernel_info(self._L.wbc_ground_terrain_kernel_info)
 
 
+@contextlib.contextmanager
+def _gait_set(plant, setter, gait):
+    """The gait as the target source of the plant's rollout for the length of the block; gait None: nothing, and no entry point of
+    include_gait/wbc_gait.h is looked up (a library from before the gait planner runs every trajectory loop)."""
+    if gait is None:
+        yield
+        return
+    set_gait = getattr(plant._L, setter)
+    _lib.check(set_gait(plant._h, gait._h))
+    try:
+        yield
+    finally:
+        set_gait(plant._h, None)     # the rollout has issued its launches: the handle goes back to trajectories
+
+
 def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=None, plant_mu=None, plant_mass_scale=None, counts=None,
                 ext_wrench=None):
     """`steps` x (target lookup at time -> ctrl tick -> plant step) on the device, on torch's current stream: wbc_plant_rollout for
     a RigidContactPlant, wbc_ground_rollout for a GroundContactPlant.  Updates q, v, time in place; counts (int32 [4, N], optional)
     accumulates the plant's flag bits.  mu / mass_scale go to the controller, plant_mu / plant_mass_scale to the plant.
     ext_wrench ([6, N], GroundContactPlant only): a world-frame wrench on the trunk held over the whole loop.
+    traj: a trajectory (planners.py), or a gait.GaitPlanner whose set_commands covers these N instances: every tick's targets and
+    mask are then the gait's at `time` (gait -> follow, if set -> tick -> plant step).
     Returns the last tick's (tau, metrics, status, targets, mask, force, flags), and for a GroundContactPlant also contact."""
     import torch
+    from .gait import GaitPlanner
     if ctrl.host_ptrs:
         raise ValueError("closed_loop: needs a device-pointer controller")
     ground = isinstance(plant, GroundContactPlant)
@@ -289,6 +308,13 @@ def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=No
     d = plant.device
     if ground:
         plant._check_terrain_n(n)
+    gait = traj if isinstance(traj, GaitPlanner) else None
+    if gait is not None:
+        if gait._n != n:
+            raise ValueError("closed_loop: the GaitPlanner's commands hold %s instances, the call has %d" % (gait._n, n))
+        if gait.device != d:
+            raise ValueError("closed_loop: the GaitPlanner lives on cuda:%d, the plant on cuda:%d" % (gait.device, d))
+    htraj = None if gait is not None else traj._h
     ptr = lambda a, rows, dt_, name, opt=False: _dev_ptr(a, rows, n, dt_, name, d, opt)
     pq, pv, pt = ptr(q, 19, torch.float64, "q"), ptr(v, 18, torch.float64, "v"), ptr(time, 0, torch.float64, "time")
     pmu, pms = ptr(mu, 0, torch.float64, "mu", True), ptr(mass_scale, 0, torch.float64, "mass_scale", True)
@@ -304,13 +330,15 @@ def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=No
     s = torch.cuda.current_stream(d).cuda_stream
     if ground:
         ct = torch.zeros((n,), dtype=torch.uint8, device=dev)
-        _lib.check(plant._L.wbc_ground_rollout(ctrl._h, plant._h, traj._h, C.c_void_p(s), int(steps), float(dt), n, n, pq, pv, pt, p(tg),
-                                               p(mk), pmu, pms, ppmu, ppms, pw, p(tau), p(met), p(st), p(f), p(ct), p(fl), pc))
+        with _gait_set(plant, "wbc_ground_set_gait", gait):
+            _lib.check(plant._L.wbc_ground_rollout(ctrl._h, plant._h, htraj, C.c_void_p(s), int(steps), float(dt), n, n, pq, pv, pt, p(tg),
+                                                   p(mk), pmu, pms, ppmu, ppms, pw, p(tau), p(met), p(st), p(f), p(ct), p(fl), pc))
         ctrl._bound_stream = s
         ctrl._keep = (tg, mk, tau, met, st, f, fl, ct, mu, mass_scale, plant_mu, plant_mass_scale, ext_wrench)
         return tau, met, st, tg, mk, f, fl, ct
-    _lib.check(plant._L.wbc_plant_rollout(ctrl._h, plant._h, traj._h, C.c_void_p(s), int(steps), float(dt), n, n, pq, pv, pt, p(tg),
-                                          p(mk), pmu, pms, ppmu, ppms, p(tau), p(met), p(st), p(f), p(fl), pc))
+    with _gait_set(plant, "wbc_plant_set_gait", gait):
+        _lib.check(plant._L.wbc_plant_rollout(ctrl._h, plant._h, htraj, C.c_void_p(s), int(steps), float(dt), n, n, pq, pv, pt, p(tg),
+                                              p(mk), pmu, pms, ppmu, ppms, p(tau), p(met), p(st), p(f), p(fl), pc))
     ctrl._bound_stream = s   # wbc_plant_rollout bound the controller to this stream (wbc_set_stream)
     ctrl._keep = (tg, mk, tau, met, st, f, fl, mu, mass_scale, plant_mu, plant_mass_scale)
     return tau, met, st, tg, mk, f, fl

@@ -17,7 +17,14 @@ can fall).  `--terrain NAME[:PARAM]` (with `--plant ground` only; terrain.SPECS)
 under the feet.  `--follow lift|fit` (with `--terrain` only; default `off`) makes the planner's level-ground targets follow that ground
 between the lookup and the tick: `lift` raises the foot and trunk heights, `fit` also turns the trunk's attitude with the line
 fitted through the planned footholds (include/wbc_ground.h).  The footholds are not re-planned and the controllers' friction pyramids
-stay about world z."""
+stay about world z.
+
+`--planner gait --gait NAME --cmd VX,VY,WZ [--cmd-spread DVX,DVY,DWZ] [--stride-scale S]` (every `--plant` but `plan`) makes the robots
+WALK: gait.GaitPlanner computes each tick's targets on the device from a velocity command in the heading frame and a yaw rate
+(include_gait/wbc_gait.h).  Instance i gets a command drawn uniformly in cmd +- spread from `--seed`.  NAME is one of TOWR's strides
+(gait.STRIDES); S scales the stride's durations and defaults to 0.5: ID at TOWR's own 1.0 s trot falls when it steps in place, walks
+backwards or climbs a slope of grade 0.2, and walks all of them at half that period (profiles/r13/gait.md, gait_sweep.md).  With
+`--plant ground` the result line also has the mean and the worst distance of the trunks from their planned (x, y)."""
 import argparse
 import json
 import sys
@@ -30,9 +37,16 @@ CONTROL = ("ID", "MPTC", "PC", "CLF")
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--control", default="ID", choices=CONTROL, help="control_method (simulate.py:13)")
-    ap.add_argument("--planner", default="basic", choices=("basic", "towr"), help="planning_method (simulate.py:12)")
+    ap.add_argument("--planner", default="basic", choices=("basic", "towr", "gait"),
+                    help="planning_method (simulate.py:12); gait: walking targets from a velocity command, computed on the device")
     ap.add_argument("--scenario", default="standing", help="basic planner: standing | orientation | raise_foot | edge")
     ap.add_argument("--messages", default=None, help="towr planner: file of concatenated 549-byte trunk_state messages")
+    ap.add_argument("--gait", default="trot", help="gait planner: the stride, one of gait.STRIDES (TOWR's stride tables)")
+    ap.add_argument("--cmd", default="0.2,0,0", help="gait planner: VX,VY,WZ -- velocity in the heading frame [m/s] and yaw rate [rad/s]")
+    ap.add_argument("--cmd-spread", default="0,0,0", help="gait planner: DVX,DVY,DWZ -- instance i's command is uniform in cmd +- spread")
+    ap.add_argument("--stride-scale", type=float, default=0.5,
+                    help="gait planner: the stride's durations times this; 0.5 because ID falls at TOWR's 1.0 s trot when it steps in "
+                         "place, walks backwards or climbs, and walks all of them at 0.5 s (module docstring)")
     ap.add_argument("--sim-time", type=float, default=6.0, help="sim_time (simulate.py:20)")
     ap.add_argument("--dt", type=float, default=None, help="dt (simulate.py:21: 5e-3; MPTC / PC default to 1e-3, DESIGN.md section 9)")
     ap.add_argument("--n", type=int, default=1, help="robot instances")
@@ -52,6 +66,22 @@ def parse(argv=None):
         a.dt = 5e-3 if a.control in ("ID", "CLF") else 1e-3
     if a.planner == "towr" and not a.messages:
         ap.error("--planner towr needs --messages FILE (a recorded trunk_state stream)")
+    if a.planner == "gait":
+        from . import gait
+        if a.plant == "plan":
+            ap.error("--planner gait needs --plant rigid or --plant ground (the plan's own rollout looks its targets up in a trajectory)")
+        if a.gait not in gait.STRIDES:
+            ap.error("--gait %s: expected one of %s" % (a.gait, ", ".join(gait.STRIDES)))
+        for name in ("cmd", "cmd_spread"):
+            try:
+                val = tuple(float(x) for x in getattr(a, name).split(","))
+            except ValueError:
+                val = ()
+            if len(val) != 3 or not all(np.isfinite(val)) or (name == "cmd_spread" and min(val) < 0):
+                ap.error("--%s: expected three finite numbers A,B,C%s" % (name.replace("_", "-"), " >= 0" if name == "cmd_spread" else ""))
+            setattr(a, name, val)
+        if not (a.stride_scale > 0 and np.isfinite(a.stride_scale)):
+            ap.error("--stride-scale must be positive and finite")
     if a.terrain is not None:
         if a.plant != "ground":
             ap.error("--terrain needs --plant ground")
@@ -67,6 +97,12 @@ def parse(argv=None):
     return a
 
 
+def draw_commands(a, n):
+    """cmd [3, n]: instance i's (vx, vy, yaw rate), uniform in a.cmd +- a.cmd_spread from a.seed"""
+    u = np.random.default_rng([a.seed, 0x6A17]).uniform(-1.0, 1.0, (3, n))
+    return np.array(a.cmd)[:, None] + np.array(a.cmd_spread)[:, None] * u
+
+
 def run(a):
     """-> dict(t [S], metrics [S, 4, n], status_nonzero, ticks, q [19, n], v [18, n], ticks_per_second)"""
     import time as _time
@@ -75,7 +111,12 @@ def run(a):
     from .planners import TowrTrunkPlanner, scenario_trajectory
     cls = {"ID": IDController, "MPTC": MPTCController, "PC": PCController, "CLF": CLFController}[a.control]
     dev = "cuda:%d" % a.device
-    if a.planner == "basic":
+    cmd = None
+    if a.planner == "gait":
+        from .gait import GaitPlanner
+        traj = GaitPlanner(a.model, strides=(a.gait,), device=a.device)
+        cmd = draw_commands(a, a.n)
+    elif a.planner == "basic":
         traj = scenario_trajectory(a.scenario, a.sim_time, a.dt, model=a.model, device=a.device)
     else:
         raw = open(a.messages, "rb").read()
@@ -103,6 +144,9 @@ def run(a):
         counts = torch.zeros((4, a.n), dtype=torch.int32, device=dev)
     q, v = torch.tensor(q0, device=dev), torch.tensor(v0, device=dev)
     time = torch.zeros(a.n, dtype=torch.float64, device=dev)
+    if cmd is not None:                 # the plan starts where the trunk stands (on a terrain: off the origin, along the normal)
+        traj.set_commands(torch.tensor(cmd, device=dev), stride_scale=torch.full((a.n,), a.stride_scale, dtype=torch.float64, device=dev),
+                          start=torch.tensor(np.stack([q0[4], q0[5], np.zeros(a.n)]), device=dev))
     steps = int(round(a.sim_time / a.dt))
     ts, mets = [], []
     ctrl.stats(reset=True)
@@ -126,6 +170,10 @@ def run(a):
         names = ("slip", "fell", "clip", "bad") if a.plant == "ground" else ("pull", "cone", "clip", "bad")
         out["plant_flags"] = {nm: int((c[b] > 0).sum()) for b, nm in enumerate(names)}      # instances that ever raised the flag
         plant.close()
+    if cmd is not None:                 # the distance of every trunk from where the law puts the body at the final time
+        plan = traj.targets(time)[0][0:2]
+        off = torch.linalg.norm(q[4:6] - plan, dim=0).cpu().numpy()
+        out["plan_offset"] = {"mean": float(np.nanmean(off)), "worst": float(np.nanmax(off))}
     ctrl.close(); traj.close()
     return out
 
@@ -142,7 +190,10 @@ def main(argv=None):
         extra = {"plant": a.plant, "terrain": a.terrain, "plant_flags": r["plant_flags"]}
         if a.plant == "ground":
             extra.update(follow=a.follow, FELL=r["plant_flags"]["fell"], SLIP=r["plant_flags"]["slip"])
-    print(json.dumps({"control": a.control, "planner": a.planner, "scenario": a.scenario if a.planner == "basic" else a.messages,
+        if "plan_offset" in r:
+            extra.update(gait=a.gait, cmd=list(a.cmd), cmd_spread=list(a.cmd_spread), stride_scale=a.stride_scale,
+                         plan_offset_mean=r["plan_offset"]["mean"], plan_offset_worst=r["plan_offset"]["worst"])
+    print(json.dumps({"control": a.control, "planner": a.planner, "scenario": a.scenario if a.planner == "basic" else a.gait if a.planner == "gait" else a.messages,
                       "n": a.n, "sim_time": a.sim_time, "dt": a.dt, "ticks": r["ticks"], "status_nonzero": r["status_nonzero"],
                       "ticks_per_second": r["ticks_per_second"], "active_set_iterations_mean": r["iters_mean"],
                       "final": {"V": float(m[-1, 0].mean()), "err": float(m[-1, 1].mean()), "Vdot": float(m[-1, 3].mean())},
