@@ -67,7 +67,8 @@
  *   reports it BAD anyway).  Non-finite values in rows that are read flow through the arithmetic and reach the tick, which answers
  *   status 2 as it does today.
  *   The limits: b and the foot slopes jump when a foothold crosses a knot; the attitude follows the fit of the four PLANNED footholds,
- *   stance and swing alike; the planners do not re-plan footholds for the terrain; and the controllers' friction pyramids stay about
+ *   stance and swing alike; the follow law does not re-plan footholds for the terrain (the gait planner does, when it is given the
+ *   terrain: include_gait_terrain/wbc_gait_terrain.h, whose targets must not be followed again); and the controllers' friction pyramids stay about
  *   world z -- on a slope of grade gamma a controller mu of at most tan(atan(mu_p) - atan|gamma|) keeps an along-slope edge force
  *   inside the plant's cone about the normal (terrain.py: pyramid_mu).
  *

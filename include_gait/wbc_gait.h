@@ -56,8 +56,10 @@
  *   get all 54 rows NaN and mask 0xF; the tick then answers status 2 as it does for any NaN target.  Other instances are not touched
  *   by them.
  *
- *   The limits.  The swing knows no terrain: over a knot the follow law (wbc_ground.h) lifts a swing target by the height under it,
- *   and the target jumps at a riser.  Footholds are not moved away from edges.  The law is a function of the time and the command
+ *   The limits.  Without a terrain set on the handle (include_gait_terrain/wbc_gait_terrain.h) the swing knows no terrain: over a
+ *   knot the follow law (wbc_ground.h) lifts a swing target by the height under it, and the target jumps at a riser; and footholds
+ *   are not moved away from edges.  With one set, the footholds keep clear of the steep pieces and the swing clears what lies between
+ *   them: that header has the law and its own limits.  The law is a function of the time and the command
  *   arrays alone: a caller may rewrite cmd, gait_id, stride_scale or start between calls, and the body pose and the footholds then
  *   jump -- there is no blended transition.  The persistent wbc_rollout (wbc.h) takes no gait: its lookup is part of the tick kernels.
  *

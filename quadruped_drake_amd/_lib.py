@@ -64,6 +64,10 @@ class WbcGaitParams(C.Structure):
                 ("wait_time", C.c_double)]
 
 
+class WbcGaitTerrainParams(C.Structure):
+    _fields_ = [("body_mode", C.c_int), ("max_grade", C.c_double), ("edge_margin", C.c_double), ("apex_max", C.c_double)]
+
+
 _P, _I, _D = C.c_void_p, C.c_int, C.c_double
 _IP, _FP, _HP = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_void_p)
 _MODEL, _PARAMS, _STATS = C.POINTER(WbcModel), C.POINTER(WbcParams), C.POINTER(WbcStats)
@@ -145,10 +149,18 @@ GAIT_PROTOTYPES = {
     "wbc_ground_set_gait": (_I, [_P, _P]),
     "wbc_plant_set_gait": (_I, [_P, _P]),
 }
+# and for include_gait_terrain/wbc_gait_terrain.h (the gait planner's terrain), held to its header by tests/test_gait_terrain_cpu.py
+_GAITTP = C.POINTER(WbcGaitTerrainParams)
+GAIT_TERRAIN_PROTOTYPES = {
+    "wbc_gait_terrain_check": (_I, [_GAITTP, _P, _I]),
+    "wbc_gait_set_terrain": (_I, [_P, _GAITTP, _P, _I, _P, _P]),
+    "wbc_gait_terrain_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
+}
 # what a library may lack: an older kernel build under A/B timing (WBC_HIP_LIB; tools/qt.py --lib) the statistics exchange, the
-# follow law and the gait planner, any library the terrain
+# follow law, the gait planner and its terrain, any library the terrain
 _MAY_LACK = ("wbc_terrain_check", "wbc_ground_set_terrain", "wbc_ground_terrain_kernel_info") + \
-    (("wbc_stats_pack", "wbc_stats_reduce") + tuple(EXT_PROTOTYPES) + tuple(GAIT_PROTOTYPES) if "WBC_HIP_LIB" in os.environ else ())
+    (("wbc_stats_pack", "wbc_stats_reduce") + tuple(EXT_PROTOTYPES) + tuple(GAIT_PROTOTYPES) + tuple(GAIT_TERRAIN_PROTOTYPES)
+     if "WBC_HIP_LIB" in os.environ else ())
 
 
 class WbcError(RuntimeError):
@@ -173,7 +185,8 @@ def lib():
         except ImportError:
             pass
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXT_PROTOTYPES.items()) + list(GAIT_PROTOTYPES.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXT_PROTOTYPES.items()) + list(GAIT_PROTOTYPES.items()) + \
+                list(GAIT_TERRAIN_PROTOTYPES.items()):
             if not (name in _MAY_LACK and not hasattr(l, name)):
                 fn = getattr(l, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -5,6 +5,11 @@
 // -- and each lane evaluates its own foot's two footholds and the body's pose: three pose evaluations, two sincos each, which is the
 // kernel's latency chain.  Lane l stores its foot's nine rows; lane 0 also the 18 body rows and the mask.  The packed table
 // (wbc_gait.hpp) is staged in LDS once per block; every load is issued before the first store; nothing is read twice.
+//
+// wbc_gait_terrain_targets_kernel (include_gait_terrain/wbc_gait_terrain.h) is the same mapping with the TERRAIN instantiations of
+// the law: the terrain table is staged in LDS beside the stride table, each lane puts its foot's two footholds on the terrain and
+// raises its swing over the knots between them, and the ground height under each foot and its two rates go round the quad by
+// wbc_quad.hpp's broadcasts for the body rows.  A handle with no terrain launches wbc_gait_targets_kernel, whose code is untouched.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -12,6 +17,7 @@
 
 #include "../../include/wbc.h"
 #include "../../include_gait/wbc_gait.h"
+#include "../../include_gait_terrain/wbc_gait_terrain.h"
 #include "wbc_gait.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
@@ -28,6 +34,13 @@ struct GaitArgs {
   const double* start;
   double* targets;
   uint8_t* mask;
+};
+
+struct GaitTerrainArgs {
+  int count;             // profiles in the table; 0: no terrain
+  const double* table;   // GAIT_TERRAIN_HEAD + count * TERRAIN_STRIDE doubles
+  const uint8_t* id;
+  const double* scale;
 };
 
 }  // namespace
@@ -61,6 +74,67 @@ __global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_targets_kernel(GaitA
   }
 }
 
+// dst[0 .. words) <- src[0 .. words) by the block's 64 lanes, eight loads in flight per lane before the first of their stores: a
+// loop of one load and one store per trip pays the memory latency once per trip, and this kernel stages three times the plain one's words
+__device__ __forceinline__ void gait_stage(double* dst, const double* src, int words) {
+  constexpr int DEPTH = 8;
+  for (int base = threadIdx.x; base < words; base += DEPTH * wbc::QUAD_BLOCK) {
+    double x[DEPTH];
+#pragma unroll
+    for (int r = 0; r < DEPTH; r++) {
+      const int k = base + r * wbc::QUAD_BLOCK;
+      x[r] = k < words ? src[k] : 0.0;
+    }
+#pragma unroll
+    for (int r = 0; r < DEPTH; r++) {
+      const int k = base + r * wbc::QUAD_BLOCK;
+      if (k < words) dst[k] = x[r];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_terrain_targets_kernel(GaitArgs a, GaitTerrainArgs ta) {
+  using namespace wbc;
+  __shared__ double lds[GAIT_TABLE_DOUBLES + GAIT_TERRAIN_DOUBLES];
+  double* const ter = lds + GAIT_TABLE_DOUBLES;
+  const int words = GAIT_HEAD + a.count * GAIT_STRIDE;                 // count <= WBC_GAIT_MAX_STRIDES: checked by wbc_gait_create
+  const int twords = GAIT_TERRAIN_HEAD + ta.count * TERRAIN_STRIDE;   // count <= TERRAIN_MAX_PROFILES: checked by wbc_gait_set_terrain
+  gait_stage(lds, a.table, words);
+  gait_stage(ter, ta.table, twords);
+  const int t = blockIdx.x * QUAD_BLOCK + threadIdx.x;
+  const int l = t & 3;
+  const int r = t >> 2;
+  const bool live = r < a.n;
+  const size_t i = (size_t)(live ? r : a.n - 1);   // quads past the batch compute on its last robot and store nothing
+  const size_t ld = (size_t)a.ld;
+  const GaitIn in = gait_load(a.time, a.cmd, a.gait_id, a.scale, a.start, ld, i);
+  const int tid = ta.id ? (int)ta.id[i] : 0;
+  const double tsc = ta.scale ? ta.scale[i] : 1.0;
+  __syncthreads();
+  const GaitGround G = gait_ground(ter, ta.count, tid, tsc);
+  GaitClock c = gait_clock(lds, a.count, in);
+  gait_clock_spoil(c, G.bad);
+  double b[18], f[9], own[3], gr[12];
+  gait_foot<true>(lds, in, c, l, f, nullptr, ter, &G, own);
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    gr[d] = qmove<qp_bcast<0>()>(own[d]);
+    gr[3 + d] = qmove<qp_bcast<1>()>(own[d]);
+    gr[6 + d] = qmove<qp_bcast<2>()>(own[d]);
+    gr[9 + d] = qmove<qp_bcast<3>()>(own[d]);
+  }
+  gait_body<true>(lds, in, c, b, ter, gr);
+  if (!live) return;
+  double* out = a.targets + i;
+#pragma unroll
+  for (int k = 0; k < 9; k++) out[(size_t)(18 + 9 * l + k) * ld] = f[k];
+  if (l == 0) {
+#pragma unroll
+    for (int k = 0; k < 18; k++) out[(size_t)k * ld] = b[k];
+    a.mask[i] = (uint8_t)c.mask;
+  }
+}
+
 struct wbc_gait_s {
   int device, count;
   double table[wbc::GAIT_TABLE_DOUBLES];
@@ -69,6 +143,8 @@ struct wbc_gait_s {
   const uint8_t* gait_id;
   const double* scale;
   const double* start;
+  double* d_terrain;       // the packed terrain table, GAIT_TERRAIN_DOUBLES doubles, allocated by the first wbc_gait_set_terrain
+  GaitTerrainArgs terrain; // count == 0: no terrain, the plain kernel
 };
 
 extern "C" {
@@ -90,16 +166,19 @@ int wbc_gait_create(const wbc_gait_params* params, const wbc_gait_stride* stride
   wbc::gait_pack(params, strides, count, g->table);
   g->d_table = nullptr;
   g->cmd = nullptr; g->gait_id = nullptr; g->scale = nullptr; g->start = nullptr;
+  g->d_terrain = nullptr;
+  g->terrain = GaitTerrainArgs{};
   *out = g;
   return 0;
 }
 
 int wbc_gait_destroy(wbc_gait g) {
   if (!g) return 0;
-  if (g->d_table) {
+  if (g->d_table || g->d_terrain) {
     wbc::DeviceGuard device_guard_(g->device);
-    (void)hipDeviceSynchronize();   // a launch still reading the table
-    (void)hipFree(g->d_table);
+    (void)hipDeviceSynchronize();   // a launch still reading the tables
+    if (g->d_table) (void)hipFree(g->d_table);
+    if (g->d_terrain) (void)hipFree(g->d_terrain);
   }
   delete g;
   return 0;
@@ -133,7 +212,10 @@ int wbc_gait_targets(wbc_gait g, void* hip_stream, int n, int ld, const double* 
   GaitArgs a;
   a.n = n; a.ld = ld; a.count = g->count; a.table = g->d_table; a.time = time; a.cmd = g->cmd; a.gait_id = g->gait_id;
   a.scale = g->scale; a.start = g->start; a.targets = targets; a.mask = contact_mask;
-  hipLaunchKernelGGL(wbc_gait_targets_kernel, wbc::plant_grid(n), dim3(wbc::QUAD_BLOCK), 0, (hipStream_t)hip_stream, a);
+  if (g->terrain.count > 0)
+    hipLaunchKernelGGL(wbc_gait_terrain_targets_kernel, wbc::plant_grid(n), dim3(wbc::QUAD_BLOCK), 0, (hipStream_t)hip_stream, a, g->terrain);
+  else
+    hipLaunchKernelGGL(wbc_gait_targets_kernel, wbc::plant_grid(n), dim3(wbc::QUAD_BLOCK), 0, (hipStream_t)hip_stream, a);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -144,6 +226,45 @@ int wbc_gait_device_(wbc_gait g) { return g->device; }
 int wbc_gait_kernel_info(wbc_gait g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
   if (!g) return wbc::misuse("wbc_gait_kernel_info: null gait handle");
   return WBC_PLANT_KERNEL_INFO(g->device, wbc_gait_targets_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
+}
+
+int wbc_gait_terrain_check(const wbc_gait_terrain_params* params, const wbc_terrain_profile* profiles, int count) {
+  const char* what = wbc::gait_terrain_error(params);
+  if (what) return wbc::misuse("wbc_gait_terrain_check", what);
+  return wbc_terrain_check(profiles, count);
+}
+
+int wbc_gait_set_terrain(wbc_gait g, const wbc_gait_terrain_params* params, const wbc_terrain_profile* profiles, int count,
+                         const uint8_t* terrain_id, const double* terrain_scale) {
+  if (!g) return wbc::misuse("wbc_gait_set_terrain: null gait handle");
+  if (!profiles || count == 0) {
+    g->terrain = GaitTerrainArgs{};
+    return 0;
+  }
+  const char* what = wbc::gait_terrain_error(params);
+  if (what) return wbc::misuse("wbc_gait_set_terrain", what);
+  const int rc = wbc_terrain_check(profiles, count);
+  if (rc) return rc;
+  what = wbc::gait_terrain_fit_error(params, g->table);
+  if (what) return wbc::misuse("wbc_gait_set_terrain", what);
+  static_assert(WBC_GROUND_MAX_PROFILES == wbc::TERRAIN_MAX_PROFILES, "the header's limit is the table's");
+  double table[wbc::GAIT_TERRAIN_DOUBLES];
+  wbc::gait_terrain_pack(params, g->table, profiles, count, table);
+  WBC_ON_DEVICE(g->device, wbc::fail);
+  if (!g->d_terrain) HIP_TRY(hipMalloc(&g->d_terrain, sizeof table));
+  HIP_TRY(hipDeviceSynchronize());   // a launch still reading the previous table
+  g->terrain = GaitTerrainArgs{};
+  HIP_TRY(hipMemcpy(g->d_terrain, table, (size_t)(wbc::GAIT_TERRAIN_HEAD + count * wbc::TERRAIN_STRIDE) * sizeof(double), hipMemcpyHostToDevice));
+  g->terrain.table = g->d_terrain;
+  g->terrain.id = terrain_id;
+  g->terrain.scale = terrain_scale;
+  g->terrain.count = count;
+  return 0;
+}
+
+int wbc_gait_terrain_kernel_info(wbc_gait g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
+  if (!g) return wbc::misuse("wbc_gait_terrain_kernel_info: null gait handle");
+  return WBC_PLANT_KERNEL_INFO(g->device, wbc_gait_terrain_targets_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
 }
 
 }  // extern "C"

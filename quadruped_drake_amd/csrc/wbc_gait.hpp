@@ -11,13 +11,24 @@
 //     [0 .. 6]  B_1 .. B_7, +inf from B_nphase on     [7] B_nphase     [8] the masks, phase j in bits 4j .. 4j+3     [9 .. 11] unused
 //     [12 + 6 (8 f + j) ..]  a, b of foot f's run around phase j; pa, pb and na, nb of the stance runs before and after it when it is
 //                            a swing run, a, b twice more when it is a stance run; a foot always in contact: -inf everywhere
+//
+// With a terrain (include_gait_terrain/wbc_gait_terrain.h; the TERRAIN instantiations of gait_foot and gait_body) a second table
+// rides beside the first: GAIT_TERRAIN_HEAD doubles of the handle's terrain parameters, then wbc_ground.hpp's packed profiles
+// (terrain_pack, TERRAIN_STRIDE doubles each), which the plant's kernels read too.
+//   ter[0] max_grade   [1] edge_margin   [2] apex_max   [3] unused
+//   ter[4 .. 7] xt_f / sum xt^2,  ter[8 .. 11] yt_f / sum yt^2: the lever arms of the attitude fit over their sums, all zero with LIFT
+//   profile p at ter + GAIT_TERRAIN_HEAD + p * TERRAIN_STRIDE
+// The scans over a profile's knots run over all 8 padded knots with selects: +inf knots hold no foothold and bound no swing, and the
+// padded pieces have slope 0, so they are never steep.
 #pragma once
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include_gait/wbc_gait.h"
+#include "../../include_gait_terrain/wbc_gait_terrain.h"
 #include "wbc_tick.hpp"
+#include "wbc_ground.hpp"
 
 // the clock's arithmetic is rounded operation by operation on every instantiation (the header fixes k, r and the run times)
 #if defined(__clang__)
@@ -37,6 +48,8 @@ constexpr int GAIT_HEAD = 12;
 constexpr int GAIT_STRIDE = 12 + 6 * 8 * 4;                                      // 204 doubles
 constexpr int GAIT_TABLE_DOUBLES = GAIT_HEAD + WBC_GAIT_MAX_STRIDES * GAIT_STRIDE;   // 3276 doubles, 26208 B
 constexpr double GAIT_SINC_SMALL = 1e-4;
+constexpr int GAIT_TERRAIN_HEAD = 12;
+constexpr int GAIT_TERRAIN_DOUBLES = GAIT_TERRAIN_HEAD + TERRAIN_MAX_PROFILES * TERRAIN_STRIDE;   // 652 doubles, 5216 B
 
 // ---------------------------------------------------------------- host: checks and the packed table
 // what is wrong with the arguments of wbc_gait_check, or nullptr
@@ -114,6 +127,43 @@ inline void gait_pack(const wbc_gait_params* P, const wbc_gait_stride* S, int co
   }
 }
 
+// what is wrong with the arguments of wbc_gait_terrain_check apart from the profiles themselves (wbc_terrain_check), or nullptr
+inline const char* gait_terrain_error(const wbc_gait_terrain_params* P) {
+  if (!P) return "null params";
+  if (P->body_mode != WBC_GAIT_BODY_LIFT && P->body_mode != WBC_GAIT_BODY_FIT) return "body_mode must be WBC_GAIT_BODY_LIFT (0) or WBC_GAIT_BODY_FIT (1)";
+  if (!(P->max_grade > 0.0) || not_finite(P->max_grade)) return "max_grade must be positive and finite";
+  if (!(P->edge_margin >= 0.0) || not_finite(P->edge_margin)) return "edge_margin must be non-negative and finite";
+  if (not_finite(P->apex_max)) return "apex_max must be finite";
+  return nullptr;
+}
+
+// what in the terrain parameters does not fit the gait whose packed table is `table`, or nullptr
+inline const char* gait_terrain_fit_error(const wbc_gait_terrain_params* P, const double* table) {
+  if (!(P->apex_max >= table[9])) return "apex_max must be at least the gait's swing_height";
+  if (P->body_mode == WBC_GAIT_BODY_FIT) {
+    const double mx = 0.25 * ((table[0] + table[2]) + (table[4] + table[6])), my = 0.25 * ((table[1] + table[3]) + (table[5] + table[7]));
+    double sxx = 0.0, syy = 0.0;
+    for (int f = 0; f < 4; f++) { sxx += (table[2 * f] - mx) * (table[2 * f] - mx); syy += (table[2 * f + 1] - my) * (table[2 * f + 1] - my); }
+    if (!(sxx > 0.0) || !(syy > 0.0)) return "body_mode FIT needs a stance that spans x and y (sum xt^2 > 0 and sum yt^2 > 0)";
+  }
+  return nullptr;
+}
+
+// ter <- the terrain parameters, the lever arms of the gait packed in `table`, and `count` checked profiles
+inline void gait_terrain_pack(const wbc_gait_terrain_params* P, const double* table, const wbc_terrain_profile* prof, int count, double* ter) {
+  ter[0] = P->max_grade; ter[1] = P->edge_margin; ter[2] = P->apex_max; ter[3] = 0.0;
+  const double mx = 0.25 * ((table[0] + table[2]) + (table[4] + table[6])), my = 0.25 * ((table[1] + table[3]) + (table[5] + table[7]));
+  double sxx = 0.0, syy = 0.0;
+  for (int f = 0; f < 4; f++) { sxx += (table[2 * f] - mx) * (table[2 * f] - mx); syy += (table[2 * f + 1] - my) * (table[2 * f + 1] - my); }
+  const bool fit = P->body_mode == WBC_GAIT_BODY_FIT;
+  for (int f = 0; f < 4; f++) {
+    ter[4 + f] = fit ? (table[2 * f] - mx) / sxx : 0.0;
+    ter[8 + f] = fit ? (table[2 * f + 1] - my) / syy : 0.0;
+  }
+  for (int p = 0; p < count; p++)
+    terrain_pack(prof[p].nk, prof[p].x0, prof[p].y0, prof[p].yaw, prof[p].s, prof[p].h, ter + GAIT_TERRAIN_HEAD + p * TERRAIN_STRIDE);
+}
+
 // ---------------------------------------------------------------- host and device: one instance
 struct GaitIn {        // what an instance brings
   double time, cx, cy, w, s, x0, y0, psi0;
@@ -175,8 +225,72 @@ WBC_HD GaitClock gait_clock(const double* table, int count, const GaitIn& in) {
   return c;
 }
 
-// the 18 body rows
-WBC_HD void gait_body(const double* table, const GaitIn& in, const GaitClock& c, double* b) {
+// the terrain an instance walks on: its packed profile and scale.  A malformed one walks on profile 0 at scale 1 and is answered
+// with NaN (the caller ORs `bad` into its clock).
+struct GaitGround {
+  bool bad;
+  const double* tab;
+  double scale;
+};
+WBC_HD GaitGround gait_ground(const double* ter, int count, int id, double scale) {
+  GaitGround g;
+  g.bad = (id >= count) | not_finite(scale);
+  g.tab = ter + GAIT_TERRAIN_HEAD + (g.bad ? 0 : id) * TERRAIN_STRIDE;
+  g.scale = g.bad ? 1.0 : scale;
+  return g;
+}
+WBC_HD void gait_clock_spoil(GaitClock& c, bool bad) {
+  c.bad |= bad;
+  c.mask = bad ? 0xFu : c.mask;
+}
+
+// The flat law's foothold (x, y) put on the terrain: moved off the first steep piece whose margin holds it unless `fixed` (a
+// start-pose foothold); s: the foothold's coordinate along the profile, z: the height there.
+WBC_HD void gait_foothold_on(const double* ter, const GaitGround& G, bool fixed, double& x, double& y, double& s, double& z) {
+  const double* tab = G.tab;
+  const double sF = (x - tab[2]) * tab[0] + (y - tab[3]) * tab[1];
+  double e = sF;
+  bool found = fixed;
+  WBC_GAIT_UNROLL
+  for (int j = 1; j < TERRAIN_MAX_KNOTS; j++) {                   // piece j of the packed profile: between knots j - 1 and j
+    const double lo = tab[4 + j - 1] - ter[1], hi = tab[4 + j] + ter[1];
+    const bool steep = fabs(G.scale * tab[12 + 3 * j + 2]) > ter[0];
+    const bool hit = steep & (sF > lo) & (sF < hi) & !found;
+    const double end = (hi - sF <= sF - lo) ? hi : lo;
+    e = hit ? end : e;
+    found |= hit;
+  }
+  x = x + (e - sF) * tab[0];
+  y = y + (e - sF) * tab[1];
+  s = e;
+  int j = 0;
+  WBC_GAIT_UNROLL
+  for (int k = 0; k < TERRAIN_MAX_KNOTS; k++) j += (e >= tab[4 + k]) ? 1 : 0;
+  const double* seg = tab + 12 + 3 * j;
+  z = G.scale * (seg[1] + seg[2] * (e - seg[0]));
+}
+
+// the apex of a swing from (sA, zA) to (sB, zB): swing_height, raised over every knot strictly between them, capped
+WBC_HD double gait_apex(const double* ter, const GaitGround& G, double swing_height, double sA, double zA, double sB, double zB) {
+  const double* tab = G.tab;
+  const double lo = fmin(sA, sB), hi = fmax(sA, sB), ds = sB - sA, dz = zB - zA;
+  double m = 0.0;
+  WBC_GAIT_UNROLL
+  for (int k = 0; k < TERRAIN_MAX_KNOTS; k++) {
+    const double sk = tab[4 + k], hk = tab[12 + 3 * (k + 1) + 1];   // knot k starts piece k + 1
+    const bool inside = (sk > lo) & (sk < hi);
+    const double lam = (sk - sA) / ds;
+    const double q = (G.scale * hk - (zA + lam * dz)) / (4.0 * lam * (1.0 - lam));
+    m = (inside & (q > m)) ? q : m;
+  }
+  return fmin(ter[2], swing_height + m);
+}
+
+// the 18 body rows.  TERRAIN: ter the terrain table and gr[3 f + d] the ground height under foot f (d = 0) and its first and second
+// time derivatives, as gait_foot hands them out.
+template <bool TERRAIN = false>
+WBC_HD void gait_body(const double* table, const GaitIn& in, const GaitClock& c, double* b, const double* ter = nullptr,
+                      const double* gr = nullptr) {
   double th, thd, thdd, x, y, cp, sp;
   gait_theta(table[10], c.pre ? 0.0 : c.tau, th, thd, thdd);
   th = c.pre ? 0.0 : th; thd = c.pre ? 0.0 : thd; thdd = c.pre ? 0.0 : thdd;
@@ -190,12 +304,30 @@ WBC_HD void gait_body(const double* table, const GaitIn& in, const GaitClock& c,
   b[9] = 0.0; b[10] = 0.0; b[11] = in.psi0 + in.w * th;
   b[12] = 0.0; b[13] = 0.0; b[14] = in.w * thd;
   b[15] = 0.0; b[16] = 0.0; b[17] = in.w * thdd;
+  if constexpr (TERRAIN) {
+    double m[3], P[3], Q[3];
+    WBC_GAIT_UNROLL
+    for (int d = 0; d < 3; d++) {
+      m[d] = 0.25 * ((gr[d] + gr[3 + d]) + (gr[6 + d] + gr[9 + d]));
+      P[d] = (ter[4] * gr[d] + ter[5] * gr[3 + d]) + (ter[6] * gr[6 + d] + ter[7] * gr[9 + d]);
+      Q[d] = (ter[8] * gr[d] + ter[9] * gr[3 + d]) + (ter[10] * gr[6 + d] + ter[11] * gr[9 + d]);
+    }
+    const double p1 = 1.0 + P[0] * P[0], q1 = 1.0 + Q[0] * Q[0];
+    b[2] = table[8] + m[0]; b[5] = m[1]; b[8] = m[2];
+    b[9] = atan(Q[0]); b[10] = 0.0 - atan(P[0]);
+    b[12] = Q[1] / q1; b[13] = 0.0 - P[1] / p1;
+    b[15] = (Q[2] * q1 - 2.0 * Q[0] * (Q[1] * Q[1])) / (q1 * q1);
+    b[16] = 0.0 - (P[2] * p1 - 2.0 * P[0] * (P[1] * P[1])) / (p1 * p1);
+  }
   WBC_GAIT_UNROLL
   for (int r = 0; r < 18; r++) b[r] = c.bad ? nan : b[r];
 }
 
-// the 9 rows of foot f; run (optional, for the tests): the start a of the run the foot is in, and u = (tau - a) / D as the rows use it
-WBC_HD void gait_foot(const double* table, const GaitIn& in, const GaitClock& c, int f, double* o, double* run = nullptr) {
+// the 9 rows of foot f; run (optional, for the tests): the start a of the run the foot is in, and u = (tau - a) / D as the rows use it.
+// TERRAIN: ter the terrain table, G the instance's ground; gr[3] <- the ground height under the foot and its two time derivatives.
+template <bool TERRAIN = false>
+WBC_HD void gait_foot(const double* table, const GaitIn& in, const GaitClock& c, int f, double* o, double* run = nullptr,
+                      const double* ter = nullptr, const GaitGround* G = nullptr, double* gr = nullptr) {
   const double* e = c.stride + 12 + 6 * (8 * f + c.phase);
   const double sx = table[2 * f], sy = table[2 * f + 1], ramp = table[10];
   double a, b, pa, pb, na, nb;
@@ -208,6 +340,7 @@ WBC_HD void gait_foot(const double* table, const GaitIn& in, const GaitClock& c,
   const bool swing = !((c.mask >> f) & 1u);
   // the two footholds: of the stance run before and after a swing run; a stance run's own, twice
   double F[2][2];
+  [[maybe_unused]] double Fs[2], Fz[2];
   WBC_GAIT_UNROLL
   for (int h = 0; h < 2; h++) {
     const double lo = h ? na : pa, hi = h ? nb : pb;
@@ -217,12 +350,15 @@ WBC_HD void gait_foot(const double* table, const GaitIn& in, const GaitClock& c,
     gait_pose(in, th, x, y, cp, sp);
     F[h][0] = x + (cp * sx - sp * sy);
     F[h][1] = y + (sp * sx + cp * sy);
+    if constexpr (TERRAIN) gait_foothold_on(ter, *G, c.pre | (lo <= 0.0), F[h][0], F[h][1], Fs[h], Fz[h]);
   }
   const double D = b - a, u = (c.tau - a) / D, w = 1.0 - u, uw = u * w;
   if (run) { run[0] = a; run[1] = u; }
   const double sg = (u * u) * u * (10.0 + u * (6.0 * u - 15.0));
   const double sgd = 30.0 * (uw * uw) / D, sgdd = 60.0 * uw * (1.0 - 2.0 * u) / (D * D);
-  const double hz = table[9] * 64.0;
+  double apex = table[9];
+  if constexpr (TERRAIN) apex = gait_apex(ter, *G, table[9], Fs[0], Fz[0], Fs[1], Fz[1]);
+  const double hz = apex * 64.0;
   const double z = hz * (uw * uw) * uw, zd = hz * 3.0 * (uw * uw) * (1.0 - 2.0 * u) / D;
   const double zdd = hz * 6.0 * uw * (1.0 + 5.0 * u * (u - 1.0)) / (D * D);
   const double dx = F[1][0] - F[0][0], dy = F[1][1] - F[0][1];
@@ -236,6 +372,15 @@ WBC_HD void gait_foot(const double* table, const GaitIn& in, const GaitClock& c,
   o[6] = swing ? dx * sgdd : 0.0;
   o[7] = swing ? dy * sgdd : 0.0;
   o[8] = swing ? zdd : 0.0;
+  if constexpr (TERRAIN) {
+    const double dz = Fz[1] - Fz[0];
+    gr[0] = swing ? Fz[0] + dz * sg : Fz[0];
+    gr[1] = swing ? dz * sgd : 0.0;
+    gr[2] = swing ? dz * sgdd : 0.0;
+    o[2] = swing ? gr[0] + z : Fz[0];
+    o[5] = swing ? gr[1] + zd : 0.0;
+    o[8] = swing ? gr[2] + zdd : 0.0;
+  }
   WBC_GAIT_UNROLL
   for (int r = 0; r < 9; r++) o[r] = c.bad ? nan : o[r];
 }

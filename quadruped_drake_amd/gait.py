@@ -5,6 +5,9 @@ contact schedule, footholds, swing splines and a base motion.  The schedule is d
 -- and once the base follows a commanded velocity the rest has a closed form (the law: the head of include_gait/wbc_gait.h).
 `GaitPlanner` evaluates it per instance on the GPU: every robot of a batch has its own command (vx, vy, yaw rate), its own stride
 and its own stride period, and no table of samples.  `plant.closed_loop` takes a GaitPlanner where it takes a trajectory.
+`GaitPlanner.set_terrain` gives the planner the plant's terrain (include_gait_terrain/wbc_gait_terrain.h): its targets are then the
+finished targets on that ground -- footholds off the risers, swings that clear the knots, a body that follows the feet -- and no
+follow pass runs after them.
 Torch tensors and torch's current stream, as in controller.py and plant.py.
 """
 import ctypes as C
@@ -73,6 +76,17 @@ def c_params(stance, height, swing_height, ramp_time, wait_time):
     return p
 
 
+BODY_MODES = ("lift", "fit")   # WBC_GAIT_BODY_LIFT, WBC_GAIT_BODY_FIT
+
+
+def c_terrain_params(body="fit", max_grade=0.5, edge_margin=0.03, apex_max=0.25):
+    """The wbc_gait_terrain_params of a body mode (a name of BODY_MODES or its number) and the three scalars."""
+    p = _lib.WbcGaitTerrainParams()
+    p.body_mode = BODY_MODES.index(body) if body in BODY_MODES else int(body)
+    p.max_grade, p.edge_margin, p.apex_max = float(max_grade), float(edge_margin), float(apex_max)
+    return p
+
+
 class GaitPlanner:
     """The targets of N walking robots, each with its own command (include_gait/wbc_gait.h).
 
@@ -96,6 +110,7 @@ class GaitPlanner:
         self._h = None
         self._n = None
         self._keep = None
+        self._terrain = None
         h = C.c_void_p()
         _lib.check(self._L.wbc_gait_create(C.byref(self.params), c_strides(self.strides), len(self.strides), self.device, C.byref(h)))
         self._h = h
@@ -122,6 +137,7 @@ class GaitPlanner:
         if self._n is None:
             raise ValueError("GaitPlanner.targets: set_commands first")
         n, d = self._n, self.device
+        self._check_terrain_n(n)
         pt = _lib.dev_ptr(time, 0, n, torch.float64, "time", d, "the planner")
         if out is None:
             out = (torch.empty((54, n), dtype=torch.float64, device="cuda:%d" % d), torch.empty((n,), dtype=torch.uint8, device="cuda:%d" % d))
@@ -132,15 +148,59 @@ class GaitPlanner:
         _lib.check(self._L.wbc_gait_targets(self._h, s, n, n, pt, ptg, pmk))
         return tg, mk
 
+    def set_terrain(self, profiles, terrain_id=None, terrain_scale=None, body="fit", max_grade=0.5, edge_margin=0.03, apex_max=0.25):
+        """Make the planner's targets the finished targets on a terrain (include_gait_terrain/wbc_gait_terrain.h): footholds on the
+        surface and moved `edge_margin` [m] clear of every piece steeper than `max_grade`, swings that clear the knots between their
+        footholds (apex at most `apex_max` [m]), a body that follows the feet -- body "lift": its height, "fit": also its pitch and
+        roll.  profiles: 1 .. 16 terrain.Profile, what GroundContactPlant.set_terrain takes; instance i walks on
+        profiles[terrain_id[i]] (uint8 [N]; None: profile 0) scaled by terrain_scale[i] (float64 [N]; None: 1.0); the tensors are kept
+        alive here.  No follow pass may run after such targets.  Synchronises the device."""
+        import torch
+        from . import terrain as _terrain
+        if body not in BODY_MODES:
+            raise ValueError("body %r: expected one of %s" % (body, ", ".join(BODY_MODES)))
+        profiles = list(profiles) if profiles is not None else []
+        if not profiles or not all(isinstance(p, _terrain.Profile) for p in profiles):
+            raise ValueError("set_terrain: profiles must be a non-empty list of terrain.Profile (clear_terrain() takes the terrain away)")
+        n = None
+        for a in (terrain_id, terrain_scale):
+            if a is not None and isinstance(a, torch.Tensor) and a.dim() == 1:
+                n = int(a.shape[0]) if n is None else n
+        pid = _lib.dev_ptr(terrain_id, 0, n, torch.uint8, "terrain_id", self.device, "the planner", True)
+        psc = _lib.dev_ptr(terrain_scale, 0, n, torch.float64, "terrain_scale", self.device, "the planner", True)
+        tp = c_terrain_params(body, max_grade, edge_margin, apex_max)
+        arr = _terrain.c_array(profiles)
+        _lib.check(self._L.wbc_gait_set_terrain(self._h, C.byref(tp), C.cast(arr, C.c_void_p), len(profiles), pid, psc))
+        self._terrain = (profiles, terrain_id, terrain_scale, n, body)
+
+    def clear_terrain(self):
+        """The plain gait again: targets about the plane z = 0, the kernel a planner without a terrain launches."""
+        _lib.check(self._L.wbc_gait_set_terrain(self._h, None, None, 0, None, None))
+        self._terrain = None
+
+    def _check_terrain_n(self, n):
+        t = getattr(self, "_terrain", None)
+        if t is not None and t[3] is not None and t[3] != n:
+            raise ValueError("the GaitPlanner's terrain_id / terrain_scale hold %d instances, the call has %d" % (t[3], n))
+
+    @property
+    def has_terrain(self):
+        return getattr(self, "_terrain", None) is not None
+
     def kernel_info(self):
         """Registers, scratch bytes per lane, LDS bytes and threads per block of the gait kernel."""
         return _lib.kernel_info(self._L.wbc_gait_kernel_info, self._h)
+
+    def terrain_kernel_info(self):
+        """kernel_info() of the kernel that runs while a terrain is set."""
+        return _lib.kernel_info(self._L.wbc_gait_terrain_kernel_info, self._h)
 
     def close(self):
         if getattr(self, "_h", None):
             self._L.wbc_gait_destroy(self._h)
             self._h = None
             self._keep = None
+            self._terrain = None
 
     def __del__(self):
         try:

@@ -208,6 +208,7 @@ class GroundContactPlant(_Plant):
         """What closed_loop does between the target lookup and the tick on this plant: "off" (the default), "lift" or "fit", as
         follow_targets.  With "off", or without a terrain, closed_loop launches what it launches without this call."""
         _lib.check(self._L.wbc_ground_set_follow(self._h, _follow_mode(mode)))
+        self._follow = ("off", "lift", "fit")[_follow_mode(mode)]
 
     def follow_kernel_info(self):
         """kernel_info() of the kernel behind follow_targets."""
@@ -293,7 +294,8 @@ def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=No
     accumulates the plant's flag bits.  mu / mass_scale go to the controller, plant_mu / plant_mass_scale to the plant.
     ext_wrench ([6, N], GroundContactPlant only): a world-frame wrench on the trunk held over the whole loop.
     traj: a trajectory (planners.py), or a gait.GaitPlanner whose set_commands covers these N instances: every tick's targets and
-    mask are then the gait's at `time` (gait -> follow, if set -> tick -> plant step).
+    mask are then the gait's at `time` (gait -> follow, if set -> tick -> plant step).  A GaitPlanner with a terrain
+    (GaitPlanner.set_terrain) gives finished targets: with a follow mode set on a plant with a terrain this raises ValueError.
     Returns the last tick's (tau, metrics, status, targets, mask, force, flags), and for a GroundContactPlant also contact."""
     import torch
     from .gait import GaitPlanner
@@ -314,6 +316,11 @@ def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=No
             raise ValueError("closed_loop: the GaitPlanner's commands hold %s instances, the call has %d" % (gait._n, n))
         if gait.device != d:
             raise ValueError("closed_loop: the GaitPlanner lives on cuda:%d, the plant on cuda:%d" % (gait.device, d))
+        if gait.has_terrain:
+            gait._check_terrain_n(n)
+            if ground and getattr(plant, "_follow", "off") != "off" and plant._terrain is not None:
+                raise ValueError("closed_loop: the GaitPlanner has a terrain, so its targets are finished; the plant's follow mode %r "
+                                 "would lift them a second time (set_follow('off'))" % (plant._follow,))
     htraj = None if gait is not None else traj._h
     ptr = lambda a, rows, dt_, name, opt=False: _dev_ptr(a, rows, n, dt_, name, d, opt)
     pq, pv, pt = ptr(q, 19, torch.float64, "q"), ptr(v, 18, torch.float64, "v"), ptr(time, 0, torch.float64, "time")

@@ -24,7 +24,10 @@ WALK: gait.GaitPlanner computes each tick's targets on the device from a velocit
 (include_gait/wbc_gait.h).  Instance i gets a command drawn uniformly in cmd +- spread from `--seed`.  NAME is one of TOWR's strides
 (gait.STRIDES); S scales the stride's durations and defaults to 0.5: ID at TOWR's own 1.0 s trot falls when it steps in place, walks
 backwards or climbs a slope of grade 0.2, and walks all of them at half that period (profiles/r13/gait.md, gait_sweep.md).  With
-`--plant ground` the result line also has the mean and the worst distance of the trunks from their planned (x, y)."""
+`--plant ground` the result line also has the mean and the worst distance of the trunks from their planned (x, y).
+`--gait-terrain lift|fit` (with `--planner gait` and `--terrain`; default `off`; excludes `--follow`) gives the plant's terrain to the
+planner (include_gait_terrain/wbc_gait_terrain.h): footholds on the surface and off the risers, swings that clear what lies between
+their footholds, a body that follows the feet (`fit`: also in pitch and roll).  That is what walks a kerb of 0.1 m."""
 import argparse
 import json
 import sys
@@ -59,6 +62,8 @@ def parse(argv=None):
     ap.add_argument("--terrain", default=None, help="--plant ground only: NAME[:PARAM], e.g. slope:0.2 (flat, slope, ramp_step, stairs, ridge)")
     ap.add_argument("--follow", default="off", choices=("off", "lift", "fit"),
                     help="--terrain only: make the targets follow the ground (lift: heights; fit: heights and the trunk's attitude)")
+    ap.add_argument("--gait-terrain", default="off", choices=("off", "lift", "fit"),
+                    help="--planner gait with --terrain only: the planner walks ON the terrain (lift: body height; fit: and its attitude)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
@@ -92,6 +97,11 @@ def parse(argv=None):
             ap.error(str(e))
     if a.follow != "off" and a.terrain is None:
         ap.error("--follow needs --terrain")
+    if a.gait_terrain != "off":
+        if a.planner != "gait" or a.terrain is None:
+            ap.error("--gait-terrain needs --planner gait and --terrain")
+        if a.follow != "off":
+            ap.error("--gait-terrain excludes --follow: the planner's targets are finished, following would lift them twice")
     if a.n < 1 or a.sim_time <= 0 or a.dt <= 0 or a.log_every < 1:
         ap.error("--n, --sim-time, --dt and --log-every must be positive")
     return a
@@ -141,6 +151,8 @@ def run(a):
                 plant.set_follow(a.follow)
                 quat, pos = terrain.stance_pose(prof, 0.0, 0.0, float(q0[6, 0]))     # square on the ground under the start
                 q0[0:4] = quat[:, None]; q0[4:7] = pos[:, None]
+                if a.gait_terrain != "off":
+                    traj.set_terrain([prof], body=a.gait_terrain)
         counts = torch.zeros((4, a.n), dtype=torch.int32, device=dev)
     q, v = torch.tensor(q0, device=dev), torch.tensor(v0, device=dev)
     time = torch.zeros(a.n, dtype=torch.float64, device=dev)
@@ -189,7 +201,7 @@ def main(argv=None):
     if a.plant != "plan":
         extra = {"plant": a.plant, "terrain": a.terrain, "plant_flags": r["plant_flags"]}
         if a.plant == "ground":
-            extra.update(follow=a.follow, FELL=r["plant_flags"]["fell"], SLIP=r["plant_flags"]["slip"])
+            extra.update(follow=a.follow, gait_terrain=a.gait_terrain, FELL=r["plant_flags"]["fell"], SLIP=r["plant_flags"]["slip"])
         if "plan_offset" in r:
             extra.update(gait=a.gait, cmd=list(a.cmd), cmd_spread=list(a.cmd_spread), stride_scale=a.stride_scale,
                          plan_offset_mean=r["plan_offset"]["mean"], plan_offset_worst=r["plan_offset"]["worst"])

@@ -1,16 +1,21 @@
 #!/usr/bin/env python3
-"""Measurements of the gait planner (include_gait/wbc_gait.h) for profiles/r13/gait.md.
+"""Measurements of the gait planner (include_gait/wbc_gait.h) for profiles/r13/gait.md and of its terrain
+(include_gait_terrain/wbc_gait_terrain.h) for profiles/r14/gait_terrain.md.
 
     python tools/gait_bench.py kernel [--n 4096] [--bursts 30] [--burst 20]
-    python tools/gait_bench.py loop --source traj|gait [--n 4096] [--steps 300] [--repeats 5]
+    python tools/gait_bench.py loop --source traj|gait|gait_terrain|gait_follow [--n 4096] [--steps 300] [--repeats 5]
 
   kernel: device time per launch of wbc_gait_targets_kernel (a trot, per-instance commands, scales and starts, times spread over
     3 s) and of the target-lookup kernel beside it: HIP events around bursts of back-to-back launches after a warm-up, the median
-    over the bursts.
+    over the bursts.  A library with the gait's terrain also gets wbc_gait_terrain_targets_kernel timed in the same process: the same
+    planner on sixteen kerbs and stairs, each instance with its own profile and scale, FIT.
   loop: time per 1 ms tick of wbc_ground_rollout at 16 substeps, MPTC, with the targets looked up in a recorded trot
     (tools/follow_bench.py's; `traj`: the launches the rollout issued before it could take a gait) or computed by the gait (`gait`:
     a trot at stride scale 0.5, commands over +-0.3 m/s and +-0.5 rad/s).  One figure per process; the caller runs them in turn.  A
     library from before the gait planner (WBC_HIP_LIB) is measured with `--source traj`, which calls nothing it lacks.
+    `gait_terrain`: the plant on sixteen kerbs and stairs and the gait on the same terrain (one terrain kernel per tick);
+    `gait_follow`: the same ground under the plain gait with the follow law in FIT after it (two kernels per tick), the path a
+    terrain gait replaces.
 Both print one JSON line."""
 import argparse
 import json
@@ -37,6 +42,18 @@ def _planner(n, seed=1):
     return p
 
 
+def _terrains(n, seed=2):
+    """sixteen kerbs and stairs, 0.3 m ahead, and per instance a profile and a scale in 0.5 .. 1.5"""
+    import numpy as np
+    import torch
+    from quadruped_drake_amd import terrain
+    profiles = [terrain.ramp_step(0.3, 0.02 + 0.01 * k) if k % 2 == 0 else terrain.stairs(0.3, 0.2, [0.02 + 0.005 * k] * 3) for k in range(16)]
+    rng = np.random.default_rng(seed)
+    tid = torch.tensor((np.arange(n) % 16).astype(np.uint8), device="cuda:0")
+    tsc = torch.tensor(rng.uniform(0.5, 1.5, n), device="cuda:0")
+    return profiles, tid, tsc
+
+
 def kernel(a):
     import numpy as np
     import torch
@@ -48,6 +65,13 @@ def kernel(a):
     out = p.targets(tm)
     res = {"n": a.n, "kernel": p.kernel_info()}
     res["gait"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
+    if hasattr(p._L, "wbc_gait_set_terrain"):
+        profiles, tid, tsc = _terrains(a.n)
+        p.set_terrain(profiles, terrain_id=tid, terrain_scale=tsc, body="fit")
+        res["terrain_kernel"] = p.terrain_kernel_info()
+        res["gait_terrain"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
+        p.clear_terrain()
+        res["gait_after_clear"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
     st_t = workloads.standing_targets("mini_cheetah", 1)[:, 0]
     K = 4000
     traj = TrunkTrajectory(np.arange(K) * 1e-3, np.tile(st_t, (K, 1)), np.full(K, 15, np.uint8), wait_time=0.0, device=0,
@@ -65,7 +89,7 @@ def loop(a):
     from quadruped_drake_amd import GroundContactPlant, MPTCController, closed_loop, workloads
     from quadruped_drake_amd.trajectory import TrunkTrajectory
     n, dt, dev = a.n, 1e-3, "cuda:0"
-    if a.source == "gait":
+    if a.source.startswith("gait"):
         src = _planner(n)
     else:
         st_t = workloads.standing_targets("mini_cheetah", 1)[:, 0]
@@ -81,6 +105,13 @@ def loop(a):
     t0 = np.random.default_rng(1).uniform(0.0, 0.6, n)
     ctrl = MPTCController(max_batch=n, device=0)
     plant = GroundContactPlant("mini_cheetah", device=0)
+    if a.source in ("gait_terrain", "gait_follow"):
+        profiles, tid, tsc = _terrains(n)
+        plant.set_terrain(profiles, terrain_id=tid, terrain_scale=tsc)
+        if a.source == "gait_terrain":
+            src.set_terrain(profiles, terrain_id=tid, terrain_scale=tsc, body="fit")
+        else:
+            plant.set_follow("fit")
     us = []
     for _ in range(a.repeats + 1):               # every repeat from the same start: the same ticks; the first is the warm-up
         q, v, t = torch.tensor(q0, device=dev), torch.tensor(v0, device=dev), torch.tensor(t0, device=dev)
@@ -105,7 +136,7 @@ def main():
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--bursts", type=int, default=30)
     ap.add_argument("--burst", type=int, default=20)
-    ap.add_argument("--source", default="traj", choices=("traj", "gait"))
+    ap.add_argument("--source", default="traj", choices=("traj", "gait", "gait_terrain", "gait_follow"))
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()

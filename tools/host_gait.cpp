@@ -44,4 +44,36 @@ int host_gait_batch(const wbc_gait_params* params, const wbc_gait_stride* stride
   return 0;
 }
 
+// The same with a terrain (include_gait_terrain/wbc_gait_terrain.h): + wbc_gait_set_terrain with host pointers.  Returns -2 on what
+// wbc_gait_terrain_check refuses in the parameters, -3 on a profile wbc_terrain_check refuses, -4 on parameters that do not fit the gait.
+int host_gait_terrain_batch(const wbc_gait_params* params, const wbc_gait_stride* strides, int count, const wbc_gait_terrain_params* tparams,
+                            const wbc_terrain_profile* profiles, int tcount, int n, int ld, const double* time, const double* cmd,
+                            const uint8_t* gait_id, const double* stride_scale, const double* start, const uint8_t* terrain_id,
+                            const double* terrain_scale, double* targets, uint8_t* contact_mask) {
+  if (gait_error(params, strides, count)) return -1;
+  if (gait_terrain_error(tparams)) return -2;
+  if (!profiles || tcount < 1 || tcount > TERRAIN_MAX_PROFILES) return -3;
+  for (int p = 0; p < tcount; p++)
+    if (terrain_profile_error(profiles[p].nk, profiles[p].x0, profiles[p].y0, profiles[p].yaw, profiles[p].s, profiles[p].h)) return -3;
+  double table[GAIT_TABLE_DOUBLES] = {0.0}, ter[GAIT_TERRAIN_DOUBLES] = {0.0};
+  gait_pack(params, strides, count, table);
+  if (gait_terrain_fit_error(tparams, table)) return -4;
+  gait_terrain_pack(tparams, table, profiles, tcount, ter);
+  for (int i = 0; i < n; i++) {
+    const GaitIn in = gait_load(time, cmd, gait_id, stride_scale, start, (size_t)ld, (size_t)i);
+    const GaitGround G = gait_ground(ter, tcount, terrain_id ? (int)terrain_id[i] : 0, terrain_scale ? terrain_scale[i] : 1.0);
+    GaitClock c = gait_clock(table, count, in);
+    gait_clock_spoil(c, G.bad);
+    double b[18], f[9], gr[12];
+    for (int l = 0; l < 4; l++) {
+      gait_foot<true>(table, in, c, l, f, nullptr, ter, &G, gr + 3 * l);
+      for (int k = 0; k < 9; k++) targets[(size_t)(18 + 9 * l + k) * ld + i] = f[k];
+    }
+    gait_body<true>(table, in, c, b, ter, gr);
+    for (int k = 0; k < 18; k++) targets[(size_t)k * ld + i] = b[k];
+    contact_mask[i] = (uint8_t)c.mask;
+  }
+  return 0;
+}
+
 }  // extern "C"
