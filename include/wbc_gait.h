@@ -1,9 +1,6 @@
 /*
  * wbc_gait.h -- C ABI of the gait planner (libwbc_hip.so): the controllers' 54 target rows and contact mask of a walking quadruped,
- * computed on the device, per instance, from a velocity command.  The conventions are those of include/wbc.h and include/wbc_ground.h;
- * the prototypes have a directory of their own because the sets that include/ and include_ext/ declare are pinned as they stand
- * (tests/test_abi_cpu.py, tests/test_follow_cpu.py); tests/test_gait_cpu.py holds this header to quadruped_drake_amd/_lib.py:
- * GAIT_PROTOTYPES by the same rules.
+ * computed on the device, per instance, from a velocity command.  The conventions are those of wbc.h and wbc_ground.h.
  *
  * The law (this project's definition).  What a trajectory optimiser gives the controllers is a contact schedule, footholds, swing
  * splines and a base motion.  Here the schedule is a table, the base follows a commanded velocity along an exact arc, and the rest
@@ -56,7 +53,7 @@
  *   get all 54 rows NaN and mask 0xF; the tick then answers status 2 as it does for any NaN target.  Other instances are not touched
  *   by them.
  *
- *   The limits.  Without a terrain set on the handle (include_gait_terrain/wbc_gait_terrain.h) the swing knows no terrain: over a
+ *   The limits.  Without a terrain set on the handle (wbc_gait_terrain.h) the swing knows no terrain: over a
  *   knot the follow law (wbc_ground.h) lifts a swing target by the height under it, and the target jumps at a riser; and footholds
  *   are not moved away from edges.  With one set, the footholds keep clear of the steep pieces and the swing clears what lies between
  *   them: that header has the law and its own limits.  The law is a function of the time and the command
@@ -72,8 +69,8 @@
 #define WBC_GAIT_H
 
 #include <stdint.h>
-#include "../include/wbc_plant.h"
-#include "../include/wbc_ground.h"
+#include "wbc_plant.h"
+#include "wbc_ground.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,11 +1,9 @@
 /*
  * wbc_gait_terrain.h -- C ABI of the gait planner's terrain (libwbc_hip.so): while a terrain is set on a gait handle, the 54 rows
  * of wbc_gait_targets are the finished targets ON that terrain -- footholds on the surface and off the risers, swings that clear what
- * lies between their two footholds, a body that follows the feet -- and no follow pass (include_ext/wbc_ground_follow.h) runs after
- * them.  With no terrain set every entry point of include_gait/wbc_gait.h does what it does without this header and launches the
- * kernel it launches without it.  The prototypes have a directory of their own because the set that include_gait/ declares is pinned
- * as it stands (tests/test_gait_cpu.py); tests/test_gait_terrain_cpu.py holds this header to quadruped_drake_amd/_lib.py:
- * GAIT_TERRAIN_PROTOTYPES by the same rules.
+ * lies between their two footholds, a body that follows the feet -- and no follow pass (wbc_ground.h) runs after
+ * them.  With no terrain set every entry point of wbc_gait.h does what it does without this header and launches the
+ * kernel it launches without it.
  *
  * The law (this project's definition).  Every quantity that is not named here is wbc_gait.h's: the clock, the runs, theta, the body's
  * arc, the flat law's footholds, u, D, sigma(u) = 10 u^3 - 15 u^4 + 6 u^5.  b(u) = 64 u^3 (1 - u)^3.
@@ -59,7 +57,7 @@
  *   guaranteed.  One pass over the steep pieces: where a level tread between two steep pieces is shorter than 2 edge_margin, a moved
  *   foothold may come to lie inside the next steep piece's margin.  e_k / (lambda_k (1 - lambda_k)) loses digits when a knot lies
  *   within rounding of a foothold.  The controllers' friction pyramids stay about world z (wbc_ground.h: pyramid_mu).  The follow law
- *   (include_ext/wbc_ground_follow.h) must not run after a terrain gait: it would lift everything a second time; a rollout of a plant
+ *   (include/wbc_ground.h) must not run after a terrain gait: it would lift everything a second time; a rollout of a plant
  *   handle with a follow mode set and a terrain gait does exactly that, and plant.closed_loop refuses the pair.  As in wbc_gait.h, a
  *   caller who rewrites the per-instance arrays between calls makes the footholds jump.
  *
@@ -70,8 +68,8 @@
 #define WBC_GAIT_TERRAIN_H
 
 #include <stdint.h>
-#include "../include/wbc_ground.h"
-#include "../include_gait/wbc_gait.h"
+#include "wbc_ground.h"
+#include "wbc_gait.h"
 
 #ifdef __cplusplus
 extern "C" {

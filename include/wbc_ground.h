@@ -43,7 +43,7 @@
  * local plane (a foot near a convex knot feels the plane of the segment under it, extended); the normal jumps at a knot; there are
  * no overhangs and no contact with a riser's face from the side beyond what the steep segment gives.
  *
- * Following the ground (wbc_ground_follow_targets, wbc_ground_set_follow of include_ext/wbc_ground_follow.h; this project's definition).  The planners' 54 target rows
+ * Following the ground (wbc_ground_follow_targets, wbc_ground_set_follow; this project's definition).  The planners' 54 target rows
  * (layout: wbc.h) are about the plane z = 0.  The follow law rewrites an instance's rows for the terrain it stands on, from its
  * profile and its terrain_scale.  H(x, y) and g(x, y) are the scaled height and the scaled slope of the piece under (x, y), with the
  * half-open pieces above; s(x, y) = (x - x0) cos(yaw) + (y - y0) sin(yaw), and for a horizontal vector u, u_s = u_x cos(yaw) +
@@ -68,7 +68,7 @@
  *   status 2 as it does today.
  *   The limits: b and the foot slopes jump when a foothold crosses a knot; the attitude follows the fit of the four PLANNED footholds,
  *   stance and swing alike; the follow law does not re-plan footholds for the terrain (the gait planner does, when it is given the
- *   terrain: include_gait_terrain/wbc_gait_terrain.h, whose targets must not be followed again); and the controllers' friction pyramids stay about
+ *   terrain: wbc_gait_terrain.h, whose targets must not be followed again); and the controllers' friction pyramids stay about
  *   world z -- on a slope of grade gamma a controller mu of at most tan(atan(mu_p) - atan|gamma|) keeps an along-slope edge force
  *   inside the plant's cone about the normal (terrain.py: pyramid_mu).
  *
@@ -164,7 +164,17 @@ int wbc_ground_terrain_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_byt
 #define WBC_FOLLOW_OFF 0
 #define WBC_FOLLOW_LIFT 1
 #define WBC_FOLLOW_FIT 2
-/* The entry points: include_ext/wbc_ground_follow.h. */
+/* The follow law in place on targets [54][ld], for the terrain set on the handle (its table, terrain_id and terrain_scale); only the
+ * rows the law changes are written: the z rows of every usable foot and of the body, in WBC_FOLLOW_FIT also the nine attitude rows.
+ * mode = WBC_FOLLOW_OFF, n = 0, or no terrain set: success, and nothing is launched.  < 0 with the message set, before any device
+ * call, for a null handle, a mode outside 0 .. 2, n < 0 or n > WBC_MAX_LD, ld < n or ld > WBC_MAX_LD, or null targets with n > 0. */
+int wbc_ground_follow_targets(wbc_ground g, void* hip_stream, int n, int ld, int mode, double* targets);
+/* What wbc_ground_rollout does between its lookup and its tick: with a mode other than WBC_FOLLOW_OFF (the default) and a terrain set,
+ * every tick runs lookup -> follow -> wbc_step -> ground step, and on return targets holds the last tick's followed targets.  With
+ * WBC_FOLLOW_OFF or no terrain set the rollout issues exactly the launches it issues without this call. */
+int wbc_ground_set_follow(wbc_ground g, int mode);
+/* wbc_ground_kernel_info of the follow kernel. */
+int wbc_ground_follow_kernel_info(wbc_ground g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads);
 
 #ifdef __cplusplus
 }

@@ -73,11 +73,12 @@ _IP, _FP, _HP = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_void_p)
 _MODEL, _PARAMS, _STATS = C.POINTER(WbcModel), C.POINTER(WbcParams), C.POINTER(WbcStats)
 _TRUNK, _ROBOT = C.POINTER(WbcTrunkState), C.POINTER(WbcRobotState)
 _PLANTP, _GROUNDP = C.POINTER(WbcPlantParams), C.POINTER(WbcGroundParams)
+_GAITP, _GAITS, _GAITTP = C.POINTER(WbcGaitParams), C.POINTER(WbcGaitStride), C.POINTER(WbcGaitTerrainParams)
 
-# name: (restype, argtypes) of every function include/wbc.h (the controller interface), include/wbc_plant.h and include/wbc_ground.h (the
-# plant steps) and include/wbc_extras.h (frozen out-of-scope exports) declare, one position per argument in the header's order
+# name: (restype, argtypes) of every function the headers of include/ declare, one position per argument in the header's order
 # (tests/test_abi_cpu.py lays each row beside the header's prototype).  A handle, a stream and a device array are _P.
 PROTOTYPES = {
+    # wbc.h: the controller interface
     "wbc_last_error": (C.c_char_p, []),
     "wbc_version": (_I, []),
     "wbc_params_default": (_I, [_I, _PARAMS]),
@@ -106,11 +107,13 @@ PROTOTYPES = {
     "wbc_traj_create": (_I, [_I, _I, c_double_p, c_double_p, c_u8_p, c_double_p, C.c_uint8, _D, _HP]),
     "wbc_traj_destroy": (_I, [_P]),
     "wbc_traj_lookup": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    # wbc_extras.h: frozen out-of-scope exports
     "wbc_robot_state_decode": (_I, [C.c_char_p, C.c_size_t, _ROBOT]),
     "wbc_robot_state_encode": (_I, [_ROBOT, C.c_char_p, C.c_size_t]),
     "wbc_robot_states_unpack": (_I, [_I, _P, _I, _I, _P, _P, _P, _P]),
     "wbc_robot_controls_pack": (_I, [_I, _P, _I, _I, _P, _IP, _IP, _P]),
     "wbc_pd_step": (_I, [_I, _P, _I, _I, _P, _P, c_double_p, _D, _D, _D, _IP, _IP, _P]),
+    # wbc_plant.h: the rigid-contact plant
     "wbc_plant_params_default": (_I, [_PLANTP]),
     "wbc_plant_create": (_I, [_MODEL, _PLANTP, _I, _HP]),
     "wbc_plant_destroy": (_I, [_P]),
@@ -118,6 +121,7 @@ PROTOTYPES = {
     "wbc_plant_step": (_I, [_P, _P, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "wbc_plant_rollout": (_I, [_P, _P, _P, _P, _I, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "wbc_plant_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
+    # wbc_ground.h: the compliant-ground plant, its terrain and the follow law
     "wbc_ground_params_default": (_I, [_MODEL, _GROUNDP]),
     "wbc_ground_create": (_I, [_MODEL, _GROUNDP, _I, _HP]),
     "wbc_ground_destroy": (_I, [_P]),
@@ -128,18 +132,10 @@ PROTOTYPES = {
     "wbc_terrain_check": (_I, [_P, _I]),
     "wbc_ground_set_terrain": (_I, [_P, _P, _I, _P, _P]),
     "wbc_ground_terrain_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
-}
-SYMBOLS = list(PROTOTYPES)
-# the same for include_ext/wbc_ground_follow.h (the follow law of the ground plant), whose prototypes tests/test_follow_cpu.py lays
-# beside this table: the set that include/*.h declares is pinned as it stands
-EXT_PROTOTYPES = {
     "wbc_ground_follow_targets": (_I, [_P, _P, _I, _I, _I, _P]),
     "wbc_ground_set_follow": (_I, [_P, _I]),
     "wbc_ground_follow_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
-}
-# and for include_gait/wbc_gait.h (the gait planner), held to its header by tests/test_gait_cpu.py
-_GAITP, _GAITS = C.POINTER(WbcGaitParams), C.POINTER(WbcGaitStride)
-GAIT_PROTOTYPES = {
+    # wbc_gait.h: the gait planner
     "wbc_gait_check": (_I, [_GAITP, _GAITS, _I]),
     "wbc_gait_create": (_I, [_GAITP, _GAITS, _I, _I, _HP]),
     "wbc_gait_destroy": (_I, [_P]),
@@ -148,19 +144,19 @@ GAIT_PROTOTYPES = {
     "wbc_gait_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
     "wbc_ground_set_gait": (_I, [_P, _P]),
     "wbc_plant_set_gait": (_I, [_P, _P]),
-}
-# and for include_gait_terrain/wbc_gait_terrain.h (the gait planner's terrain), held to its header by tests/test_gait_terrain_cpu.py
-_GAITTP = C.POINTER(WbcGaitTerrainParams)
-GAIT_TERRAIN_PROTOTYPES = {
+    # wbc_gait_terrain.h: the gait planner's terrain
     "wbc_gait_terrain_check": (_I, [_GAITTP, _P, _I]),
     "wbc_gait_set_terrain": (_I, [_P, _GAITTP, _P, _I, _P, _P]),
     "wbc_gait_terrain_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
 }
-# what a library may lack: an older kernel build under A/B timing (WBC_HIP_LIB; tools/qt.py --lib) the statistics exchange, the
-# follow law, the gait planner and its terrain, any library the terrain
-_MAY_LACK = ("wbc_terrain_check", "wbc_ground_set_terrain", "wbc_ground_terrain_kernel_info") + \
-    (("wbc_stats_pack", "wbc_stats_reduce") + tuple(EXT_PROTOTYPES) + tuple(GAIT_PROTOTYPES) + tuple(GAIT_TERRAIN_PROTOTYPES)
-     if "WBC_HIP_LIB" in os.environ else ())
+SYMBOLS = list(PROTOTYPES)
+# the names newer than the oldest kernel build still timed against (A/B timing: WBC_HIP_LIB; tools/qt.py --lib): the statistics
+# exchange, the follow law, the gait planner and its terrain
+_NEWER = ("wbc_stats_pack", "wbc_stats_reduce", "wbc_ground_follow_targets", "wbc_ground_set_follow", "wbc_ground_follow_kernel_info",
+          "wbc_gait_check", "wbc_gait_create", "wbc_gait_destroy", "wbc_gait_set_commands", "wbc_gait_targets", "wbc_gait_kernel_info",
+          "wbc_ground_set_gait", "wbc_plant_set_gait", "wbc_gait_terrain_check", "wbc_gait_set_terrain", "wbc_gait_terrain_kernel_info")
+# what a library may lack: any library the terrain, a library under A/B timing the newer names too
+_MAY_LACK = ("wbc_terrain_check", "wbc_ground_set_terrain", "wbc_ground_terrain_kernel_info") + (_NEWER if "WBC_HIP_LIB" in os.environ else ())
 
 
 class WbcError(RuntimeError):
@@ -185,8 +181,7 @@ def lib():
         except ImportError:
             pass
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXT_PROTOTYPES.items()) + list(GAIT_PROTOTYPES.items()) + \
-                list(GAIT_TERRAIN_PROTOTYPES.items()):
+        for name, (restype, argtypes) in PROTOTYPES.items():
             if not (name in _MAY_LACK and not hasattr(l, name)):
                 fn = getattr(l, name)
                 fn.restype, fn.argtypes = restype, argtypes

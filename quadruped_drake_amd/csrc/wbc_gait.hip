@@ -1,4 +1,4 @@
-// wbc_gait.hip -- the gait planner (include_gait/wbc_gait.h): kernel and C ABI.
+// wbc_gait.hip -- the gait planner (include/wbc_gait.h): kernel and C ABI.
 //
 // Mapping of the plant kernels (wbc_quad.hpp): a quad of lanes per robot, one foot per lane, 16 robots per wavefront.  Every lane
 // loads its robot's nine inputs, the clock (stride, phase, mask) is replicated on the quad -- the same instructions on the same bits
@@ -6,7 +6,7 @@
 // kernel's latency chain.  Lane l stores its foot's nine rows; lane 0 also the 18 body rows and the mask.  The packed table
 // (wbc_gait.hpp) is staged in LDS once per block; every load is issued before the first store; nothing is read twice.
 //
-// wbc_gait_terrain_targets_kernel (include_gait_terrain/wbc_gait_terrain.h) is the same mapping with the TERRAIN instantiations of
+// wbc_gait_terrain_targets_kernel (include/wbc_gait_terrain.h) is the same mapping with the TERRAIN instantiations of
 // the law: the terrain table is staged in LDS beside the stride table, each lane puts its foot's two footholds on the terrain and
 // raises its swing over the knots between them, and the ground height under each foot and its two rates go round the quad by
 // wbc_quad.hpp's broadcasts for the body rows.  A handle with no terrain launches wbc_gait_targets_kernel, whose code is untouched.
@@ -16,8 +16,8 @@
 #include <stdio.h>
 
 #include "../../include/wbc.h"
-#include "../../include_gait/wbc_gait.h"
-#include "../../include_gait_terrain/wbc_gait_terrain.h"
+#include "../../include/wbc_gait.h"
+#include "../../include/wbc_gait_terrain.h"
 #include "wbc_gait.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
@@ -220,7 +220,7 @@ int wbc_gait_targets(wbc_gait g, void* hip_stream, int n, int ld, const double* 
   return 0;
 }
 
-// internal (not in include_gait/wbc_gait.h): the handle's device, for the plants' wbc_*_set_gait
+// internal (not in include/wbc_gait.h): the handle's device, for the plants' wbc_*_set_gait
 int wbc_gait_device_(wbc_gait g) { return g->device; }
 
 int wbc_gait_kernel_info(wbc_gait g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {

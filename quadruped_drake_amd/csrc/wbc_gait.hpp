@@ -1,4 +1,4 @@
-// wbc_gait.hpp -- the gait planner's law (include_gait/wbc_gait.h, "The law"; product code): its one text, instantiated by
+// wbc_gait.hpp -- the gait planner's law (include/wbc_gait.h, "The law"; product code): its one text, instantiated by
 // wbc_gait_targets_kernel (wbc_gait.hip, a quad of lanes per robot, one foot per lane) and by tools/host_gait.cpp.
 //
 // The host packs the parameters and every stride into one table of doubles (gait_pack): per (foot, phase) the bounds of the run the
@@ -12,7 +12,7 @@
 //     [12 + 6 (8 f + j) ..]  a, b of foot f's run around phase j; pa, pb and na, nb of the stance runs before and after it when it is
 //                            a swing run, a, b twice more when it is a stance run; a foot always in contact: -inf everywhere
 //
-// With a terrain (include_gait_terrain/wbc_gait_terrain.h; the TERRAIN instantiations of gait_foot and gait_body) a second table
+// With a terrain (include/wbc_gait_terrain.h; the TERRAIN instantiations of gait_foot and gait_body) a second table
 // rides beside the first: GAIT_TERRAIN_HEAD doubles of the handle's terrain parameters, then wbc_ground.hpp's packed profiles
 // (terrain_pack, TERRAIN_STRIDE doubles each), which the plant's kernels read too.
 //   ter[0] max_grade   [1] edge_margin   [2] apex_max   [3] unused
@@ -25,8 +25,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "../../include_gait/wbc_gait.h"
-#include "../../include_gait_terrain/wbc_gait_terrain.h"
+#include "../../include/wbc_gait.h"
+#include "../../include/wbc_gait_terrain.h"
 #include "wbc_tick.hpp"
 #include "wbc_ground.hpp"
 

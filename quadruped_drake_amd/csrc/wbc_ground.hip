@@ -14,8 +14,7 @@
 
 #include "../../include/wbc.h"
 #include "../../include/wbc_ground.h"
-#include "../../include_ext/wbc_ground_follow.h"
-#include "../../include_gait/wbc_gait.h"
+#include "../../include/wbc_gait.h"
 #include "wbc_model.hpp"
 #include "wbc_tick.hpp"
 #include "wbc_ground.hpp"

@@ -12,7 +12,7 @@
 
 #include "../../include/wbc.h"
 #include "../../include/wbc_plant.h"
-#include "../../include_gait/wbc_gait.h"
+#include "../../include/wbc_gait.h"
 #include "wbc_model.hpp"
 #include "wbc_tick.hpp"
 #include "wbc_plant.hpp"

@@ -49,7 +49,7 @@ inline dim3 plant_grid(int n) { return dim3((unsigned)(((size_t)n * 4 + QUAD_BLO
 // arguments were checked by the caller.  A host-pointer controller handle is refused before anything is launched.
 // `between()` runs after the lookup and before the tick, on the targets the lookup wrote; by default it does nothing.
 // `source(traj, hip_stream, n, ld, time, targets, contact_mask)` writes a tick's targets and mask; by default it is the lookup in
-// `traj` (a gait set on the plant handle takes its place: include_gait/wbc_gait.h).
+// `traj` (a gait set on the plant handle takes its place: include/wbc_gait.h).
 struct NoRolloutHook {
   int operator()() const { return 0; }
 };

@@ -1,11 +1,11 @@
-"""Gait planner on the device (include_gait/wbc_gait.h): walking targets from a velocity command.
+"""Gait planner on the device (include/wbc_gait.h): walking targets from a velocity command.
 
 The reference gets its walking `trunk_input` from TOWR, which is out of scope here.  As far as the controllers see it, that is a
 contact schedule, footholds, swing splines and a base motion.  The schedule is data -- TOWR's stride tables, restated in `STRIDES`
--- and once the base follows a commanded velocity the rest has a closed form (the law: the head of include_gait/wbc_gait.h).
+-- and once the base follows a commanded velocity the rest has a closed form (the law: the head of include/wbc_gait.h).
 `GaitPlanner` evaluates it per instance on the GPU: every robot of a batch has its own command (vx, vy, yaw rate), its own stride
 and its own stride period, and no table of samples.  `plant.closed_loop` takes a GaitPlanner where it takes a trajectory.
-`GaitPlanner.set_terrain` gives the planner the plant's terrain (include_gait_terrain/wbc_gait_terrain.h): its targets are then the
+`GaitPlanner.set_terrain` gives the planner the plant's terrain (include/wbc_gait_terrain.h): its targets are then the
 finished targets on that ground -- footholds off the risers, swings that clear the knots, a body that follows the feet -- and no
 follow pass runs after them.
 Torch tensors and torch's current stream, as in controller.py and plant.py.
@@ -88,7 +88,7 @@ def c_terrain_params(body="fit", max_grade=0.5, edge_margin=0.03, apex_max=0.25)
 
 
 class GaitPlanner:
-    """The targets of N walking robots, each with its own command (include_gait/wbc_gait.h).
+    """The targets of N walking robots, each with its own command (include/wbc_gait.h).
 
     model: a name of workloads.STAND_FEET, which gives the nominal stance and height (or pass stance [4, 2] and height);
     strides: up to 16 strides, names of STRIDES or (durations, masks) pairs; instance i walks strides[gait_id[i]].
@@ -149,7 +149,7 @@ class GaitPlanner:
         return tg, mk
 
     def set_terrain(self, profiles, terrain_id=None, terrain_scale=None, body="fit", max_grade=0.5, edge_margin=0.03, apex_max=0.25):
-        """Make the planner's targets the finished targets on a terrain (include_gait_terrain/wbc_gait_terrain.h): footholds on the
+        """Make the planner's targets the finished targets on a terrain (include/wbc_gait_terrain.h): footholds on the
         surface and moved `edge_margin` [m] clear of every piece steeper than `max_grade`, swings that clear the knots between their
         footholds (apex at most `apex_max` [m]), a body that follows the feet -- body "lift": its height, "fit": also its pitch and
         roll.  profiles: 1 .. 16 terrain.Profile, what GroundContactPlant.set_terrain takes; instance i walks on

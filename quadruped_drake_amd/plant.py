@@ -275,7 +275,7 @@ class GroundContactPlant(_Plant):
 @contextlib.contextmanager
 def _gait_set(plant, setter, gait):
     """The gait as the target source of the plant's rollout for the length of the block; gait None: nothing, and no entry point of
-    include_gait/wbc_gait.h is looked up (a library from before the gait planner runs every trajectory loop)."""
+    include/wbc_gait.h is looked up (a library from before the gait planner runs every trajectory loop)."""
     if gait is None:
         yield
         return

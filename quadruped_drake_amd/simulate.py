@@ -21,12 +21,12 @@ stay about world z.
 
 `--planner gait --gait NAME --cmd VX,VY,WZ [--cmd-spread DVX,DVY,DWZ] [--stride-scale S]` (every `--plant` but `plan`) makes the robots
 WALK: gait.GaitPlanner computes each tick's targets on the device from a velocity command in the heading frame and a yaw rate
-(include_gait/wbc_gait.h).  Instance i gets a command drawn uniformly in cmd +- spread from `--seed`.  NAME is one of TOWR's strides
+(include/wbc_gait.h).  Instance i gets a command drawn uniformly in cmd +- spread from `--seed`.  NAME is one of TOWR's strides
 (gait.STRIDES); S scales the stride's durations and defaults to 0.5: ID at TOWR's own 1.0 s trot falls when it steps in place, walks
 backwards or climbs a slope of grade 0.2, and walks all of them at half that period (profiles/r13/gait.md, gait_sweep.md).  With
 `--plant ground` the result line also has the mean and the worst distance of the trunks from their planned (x, y).
 `--gait-terrain lift|fit` (with `--planner gait` and `--terrain`; default `off`; excludes `--follow`) gives the plant's terrain to the
-planner (include_gait_terrain/wbc_gait_terrain.h): footholds on the surface and off the risers, swings that clear what lies between
+planner (include/wbc_gait_terrain.h): footholds on the surface and off the risers, swings that clear what lies between
 their footholds, a body that follows the feet (`fit`: also in pitch and roll).  That is what walks a kerb of 0.1 m."""
 import argparse
 import json

@@ -1,4 +1,4 @@
-"""The gait planner's law restated in numpy from the sentences at the head of include_gait/wbc_gait.h (tests only; shares no code with
+"""The gait planner's law restated in numpy from the sentences at the head of include/wbc_gait.h (tests only; shares no code with
 csrc/wbc_gait.hpp and knows nothing of its packed table).  Every function takes `dtype`: np.float64, or np.longdouble for the
 extended-precision answer the CPU tests measure their bars with.  The stride's boundaries B_j are summed in double in either case:
 that is the law's definition, not a rounding of it."""

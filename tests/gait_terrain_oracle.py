@@ -1,4 +1,4 @@
-"""The gait planner's terrain law restated in numpy from the sentences at the head of include_gait_terrain/wbc_gait_terrain.h (tests
+"""The gait planner's terrain law restated in numpy from the sentences at the head of include/wbc_gait_terrain.h (tests
 only; shares no code with csrc/wbc_gait.hpp and knows nothing of its packed tables).  What that header takes from wbc_gait.h -- the
 clock, the runs, theta, the body's arc -- is gait_oracle.py's restatement of it.  Every function takes `dtype`: np.float64, or
 np.longdouble for the extended-precision answer the CPU tests measure their bars with."""

@@ -1,5 +1,5 @@
 """ctypes view of host_gait_terrain_batch of tools/libhost_gait.so: the gait planner's law with a terrain
-(include_gait_terrain/wbc_gait_terrain.h), the TERRAIN instantiations of csrc/wbc_gait.hpp on the host (tests only).  run() takes
+(include/wbc_gait_terrain.h), the TERRAIN instantiations of csrc/wbc_gait.hpp on the host (tests only).  run() takes
 the planner as host_gait.run takes it, the terrain as gait.GaitPlanner.set_terrain does, and numpy arrays."""
 import ctypes as C
 

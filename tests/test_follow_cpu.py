@@ -224,56 +224,6 @@ def test_abi_follow_misuse_without_device():
     assert (fo.OFF, fo.LIFT, fo.FIT) == (0, 1, 2) and hf.MODES == plant.FOLLOW_MODES
 
 
-def _ext_header_prototypes():
-    """{name: (return type, [argument types])} of every `ret name(args);` in include_ext/*.h, read as tests/test_abi_cpu.py reads
-    include/*.h"""
-    import glob
-    import re
-    protos = {}
-    for f in sorted(glob.glob(os.path.join(ROOT, "include_ext", "*.h"))):
-        text = re.sub(r"/\*.*?\*/", "", open(f).read(), flags=re.S)
-        for ret, name, args in re.findall(r"^((?:const )?\w+\s*\**)\s*(wbc_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-            types = []
-            for a in ([] if args.strip() == "void" else args.split(",")):
-                m = re.match(r"^(?:const )?(\w+)\s*(\**)\s*\w+$", " ".join(a.split()))
-                assert m, (name, a)
-                types.append(m.group(1) + m.group(2))
-            assert name not in protos, name
-            protos[name] = (" ".join(ret.replace("const ", "").split()).replace(" *", "*"), types)
-    return protos
-
-
-def test_ext_prototype_table_equals_its_header(tmp_path):
-    """include_ext/wbc_ground_follow.h against _lib.EXT_PROTOTYPES, from which lib() binds the three entry points, by the rules of
-    tests/test_abi_cpu.py (its _prototype_mismatches): the same functions, return types, argument counts and, position by position,
-    by-value type and pointer-ness.  The library exports each of them, none of them is also in a header of include/, the header is
-    C99 on its own, and a doctored table is caught."""
-    import subprocess
-    import test_abi_cpu as abi
-    from quadruped_drake_amd import _lib
-    header = _ext_header_prototypes()
-    assert sorted(header) == ["wbc_ground_follow_kernel_info", "wbc_ground_follow_targets", "wbc_ground_set_follow"]
-    assert header["wbc_ground_follow_targets"] == ("int", ["wbc_ground", "void*", "int", "int", "int", "double*"])
-    assert abi._prototype_mismatches(header, _lib.EXT_PROTOTYPES, _lib) == []
-    assert not set(header) & set(abi._header_prototypes()) and not set(_lib.EXT_PROTOTYPES) & set(_lib.PROTOTYPES)
-    L = _lib.lib()
-    for name, (restype, argtypes) in _lib.EXT_PROTOTYPES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
-    t = dict(_lib.EXT_PROTOTYPES)
-    res, args = t["wbc_ground_follow_targets"]
-    t["wbc_ground_follow_targets"] = (res, args[:4] + args[5:])                        # the mode dropped
-    bad = abi._prototype_mismatches(header, t, _lib)
-    assert len(bad) == 1 and bad[0].startswith("wbc_ground_follow_targets: 6 arguments in the header, 5"), bad
-    t = dict(_lib.EXT_PROTOTYPES)
-    t["wbc_ground_set_follow"] = (res, [C.c_int, C.c_void_p])                          # handle and mode swapped
-    assert len(abi._prototype_mismatches(header, t, _lib)) == 2
-    src = tmp_path / "ext.c"
-    src.write_text('#include "wbc_ground_follow.h"\nint main(void) { return WBC_FOLLOW_FIT - 2; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include_ext"), "-c", "-o",
-                    str(tmp_path / "ext.o"), str(src)], check=True, capture_output=True)
-
-
 def test_simulate_follow_arguments_and_pyramid_mu():
     from quadruped_drake_amd import simulate
     assert simulate.parse([]).follow == "off"

@@ -1,4 +1,4 @@
-"""The gait planner (include_gait/wbc_gait.h), no GPU: the host instantiation of csrc/wbc_gait.hpp (tests/host_gait.py) against the
+"""The gait planner (include/wbc_gait.h), no GPU: the host instantiation of csrc/wbc_gait.hpp (tests/host_gait.py) against the
 numpy restatement of the header's sentences (tests/gait_oracle.py), the half-open rule on exact boundaries, relations that need no
 oracle, the argument checks that return before any device is touched, the binding table against the header, gait.STRIDES against
 the reference's text, malformed instances, and the closed loop on the host twins: ID walking at a commanded velocity on the plane
@@ -385,28 +385,31 @@ def test_abi_gait_misuse_without_device():
 
 
 def test_closed_loop_with_a_trajectory_touches_no_entry_point_of_the_gait(monkeypatch):
-    """A library from before the gait planner (WBC_HIP_LIB: the A/B timing of tools/*_bench.py) lacks every name of GAIT_PROTOTYPES,
-    and lib() leaves them unbound.  closed_loop with an ordinary trajectory must then run as it did: here both plants' loops are
+    """A library from before the gait planner (WBC_HIP_LIB: the A/B timing of tools/*_bench.py) lacks every name that
+    include/wbc_gait.h declares, and lib() leaves them unbound.  closed_loop with an ordinary trajectory must then run as it did: here both plants' loops are
     driven, without a device, over a stand-in library that raises on any of those names and records the rollout it is asked for."""
     import types
     import torch
+    import test_abi_cpu as abi
     from quadruped_drake_amd import _lib, plant
+    gait_names = set(abi._header_prototypes("wbc_gait.h"))
+    assert len(gait_names) == 8
 
     class OldLibrary:
         def __init__(self):
             self.calls = []
 
         def __getattr__(self, name):
-            if name in _lib.GAIT_PROTOTYPES:
+            if name in gait_names:
                 raise AttributeError("undefined symbol: " + name)
-            assert name in _lib.PROTOTYPES, name
+            assert name in _lib.PROTOTYPES and name not in _lib._NEWER, name
 
             def call(*args):
                 self.calls.append((name, args))
                 return 0
             return call
 
-    assert "WBC_HIP_LIB" in os.environ or not set(_lib.GAIT_PROTOTYPES) & set(_lib._MAY_LACK)
+    assert "WBC_HIP_LIB" in os.environ or not gait_names & set(_lib._MAY_LACK)
     monkeypatch.setattr(plant, "_dev_ptr", lambda a, *rest: None if a is None else C.c_void_p(a.data_ptr()))
     monkeypatch.setattr(torch.cuda, "current_stream", lambda d=None: types.SimpleNamespace(cuda_stream=0))
     n = 3
@@ -426,67 +429,6 @@ def test_closed_loop_with_a_trajectory_touches_no_entry_point_of_the_gait(monkey
         with pytest.raises(AttributeError, match="set_gait"):
             plant.closed_loop(ctrl, p, g, 4, 5e-3, q, v, tm)
         g._h = None
-
-
-def _gait_header_prototypes():
-    """{name: (return type, [argument types])} of every `ret name(args);` in include_gait/*.h, read as tests/test_abi_cpu.py reads
-    include/*.h"""
-    import glob
-    protos = {}
-    for f in sorted(glob.glob(os.path.join(ROOT, "include_gait", "*.h"))):
-        text = re.sub(r"/\*.*?\*/", "", open(f).read(), flags=re.S)
-        text = re.sub(r"typedef struct \{[^}]*\}[^;]*;", "", text)
-        for ret, name, args in re.findall(r"^((?:const )?\w+\s*\**)\s*(wbc_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-            types = []
-            for a in ([] if args.strip() == "void" else args.split(",")):
-                m = re.match(r"^(?:const )?(\w+)\s*(\**)\s*\w+$", " ".join(a.split()))
-                assert m, (name, a)
-                types.append(m.group(1) + m.group(2))
-            assert name not in protos, name
-            protos[name] = (" ".join(ret.replace("const ", "").split()).replace(" *", "*"), types)
-    return protos
-
-
-def test_gait_prototype_table_equals_its_header(tmp_path, monkeypatch):
-    """include_gait/wbc_gait.h against _lib.GAIT_PROTOTYPES, from which lib() binds the eight entry points, by the rules of
-    tests/test_abi_cpu.py (its _prototype_mismatches, told of the new handle type and the two new structs).  The library exports each
-    of them, none of them is in a header of include/ or include_ext/, the header is C99 on its own, and a doctored table is caught."""
-    import subprocess
-    import test_abi_cpu as abi
-    import test_follow_cpu as follow
-    from quadruped_drake_amd import _lib
-    monkeypatch.setattr(abi, "_HANDLES", abi._HANDLES + ("wbc_gait",))
-    monkeypatch.setattr(abi, "_MIRRORS", dict(abi._MIRRORS, wbc_gait_params="WbcGaitParams", wbc_gait_stride="WbcGaitStride"))
-    header = _gait_header_prototypes()
-    assert sorted(header) == sorted(["wbc_gait_check", "wbc_gait_create", "wbc_gait_destroy", "wbc_gait_set_commands", "wbc_gait_targets",
-                                     "wbc_gait_kernel_info", "wbc_ground_set_gait", "wbc_plant_set_gait"])
-    assert header["wbc_gait_targets"] == ("int", ["wbc_gait", "void*", "int", "int", "double*", "double*", "uint8_t*"])
-    assert header["wbc_gait_create"] == ("int", ["wbc_gait_params*", "wbc_gait_stride*", "int", "int", "wbc_gait*"])
-    assert abi._prototype_mismatches(header, _lib.GAIT_PROTOTYPES, _lib) == []
-    others = set(abi._header_prototypes()) | set(follow._ext_header_prototypes())
-    assert not set(header) & others and not set(_lib.GAIT_PROTOTYPES) & (set(_lib.PROTOTYPES) | set(_lib.EXT_PROTOTYPES))
-    L = _lib.lib()
-    for name, (restype, argtypes) in _lib.GAIT_PROTOTYPES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
-    t = dict(_lib.GAIT_PROTOTYPES)
-    res, args = t["wbc_gait_targets"]
-    t["wbc_gait_targets"] = (res, args[:3] + args[4:])                                  # ld dropped
-    bad = abi._prototype_mismatches(header, t, _lib)
-    assert len(bad) == 1 and bad[0].startswith("wbc_gait_targets: 7 arguments in the header, 6"), bad
-    t = dict(_lib.GAIT_PROTOTYPES)
-    t["wbc_gait_create"] = (res, [_lib._GAITS, _lib._GAITP] + t["wbc_gait_create"][1][2:])     # params and strides swapped
-    assert len(abi._prototype_mismatches(header, t, _lib)) == 2
-    t = dict(_lib.GAIT_PROTOTYPES)
-    del t["wbc_plant_set_gait"]
-    assert abi._prototype_mismatches(header, t, _lib) == ["wbc_plant_set_gait: declared in the headers, missing from the table"]
-    assert C.sizeof(_lib.WbcGaitStride) == 80 and C.sizeof(_lib.WbcGaitParams) == 96
-    src = tmp_path / "gait.c"
-    src.write_text('#include "wbc_gait.h"\nint main(void) { return (int)sizeof(wbc_gait_stride) - 80 + (int)sizeof(wbc_gait_params) - 96 '
-                   '+ WBC_GAIT_MAX_PHASES - 8 + WBC_GAIT_MAX_STRIDES - 16; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include_gait"), "-o",
-                    str(tmp_path / "gait"), str(src)], check=True, capture_output=True)
-    assert subprocess.run([str(tmp_path / "gait")]).returncode == 0
 
 
 # ---- gait.STRIDES against the reference's text

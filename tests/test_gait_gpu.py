@@ -1,4 +1,4 @@
-"""The gait planner on the MI355X (include_gait/wbc_gait.h; gait.GaitPlanner): wbc_gait_targets_kernel against the host instantiation
+"""The gait planner on the MI355X (include/wbc_gait.h; gait.GaitPlanner): wbc_gait_targets_kernel against the host instantiation
 of the same header (tests/host_gait.py) at the bars of tests/test_gait_cpu.py, malformed instances in every robot slot of a
 wavefront, its resources, the gait as the target source of wbc_ground_rollout and wbc_plant_rollout against the same launches issued
 by hand, and ID walking five commands at once on the compliant ground."""

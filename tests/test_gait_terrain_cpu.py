@@ -1,4 +1,4 @@
-"""The gait planner's terrain (include_gait_terrain/wbc_gait_terrain.h), no GPU: the host instantiation of the TERRAIN law of
+"""The gait planner's terrain (include/wbc_gait_terrain.h), no GPU: the host instantiation of the TERRAIN law of
 csrc/wbc_gait.hpp (tests/host_gait_terrain.py) against the numpy restatement of the header's sentences (tests/gait_terrain_oracle.py),
 relations that need no oracle, the clearance of every swing over random profiles, continuity and central differences, malformed
 instances, the argument checks that return before any device is touched, the binding table against the header, and the closed loop
@@ -10,7 +10,6 @@ double and in extended precision on the same inputs ("GAIT-TERRAIN ..." lines pr
 import ctypes as C
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -422,66 +421,6 @@ def test_abi_gait_terrain_misuse_without_device():
     assert hgt.run(["trot"], [tr.flat()], t1, c1, stance=[[0.2, 0.1, 0], [0.2, -0.1, 0], [0.2, 0.05, 0], [0.2, -0.05, 0]], rc=True) == -4
     with pytest.raises(ValueError):
         gait.c_terrain_params(body="tilt")
-
-
-def _header_prototypes():
-    """{name: (return type, [argument types])} of every `ret name(args);` in include_gait_terrain/*.h, read as test_gait_cpu reads
-    include_gait/*.h"""
-    import glob
-    protos = {}
-    for f in sorted(glob.glob(os.path.join(ROOT, "include_gait_terrain", "*.h"))):
-        text = re.sub(r"/\*.*?\*/", "", open(f).read(), flags=re.S)
-        text = re.sub(r"typedef struct \{[^}]*\}[^;]*;", "", text)
-        for ret, name, args in re.findall(r"^((?:const )?\w+\s*\**)\s*(wbc_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-            types = []
-            for a in ([] if args.strip() == "void" else args.split(",")):
-                m = re.match(r"^(?:const )?(\w+)\s*(\**)\s*\w+$", " ".join(a.split()))
-                assert m, (name, a)
-                types.append(m.group(1) + m.group(2))
-            assert name not in protos, name
-            protos[name] = (" ".join(ret.replace("const ", "").split()).replace(" *", "*"), types)
-    return protos
-
-
-def test_gait_terrain_prototype_table_equals_its_header(tmp_path, monkeypatch):
-    """include_gait_terrain/wbc_gait_terrain.h against _lib.GAIT_TERRAIN_PROTOTYPES by the rules of tests/test_abi_cpu.py, as
-    test_gait_prototype_table_equals_its_header holds the gait's: the library exports and binds each name, the table is disjoint from
-    the other three and its header from theirs, the eight gait entry points are still exactly eight, the header is C99 on its own,
-    and a doctored table is caught."""
-    import subprocess
-    import test_abi_cpu as abi
-    import test_follow_cpu as follow
-    from quadruped_drake_amd import _lib
-    monkeypatch.setattr(abi, "_HANDLES", abi._HANDLES + ("wbc_gait",))
-    monkeypatch.setattr(abi, "_MIRRORS", dict(abi._MIRRORS, wbc_gait_terrain_params="WbcGaitTerrainParams"))
-    header = _header_prototypes()
-    assert sorted(header) == ["wbc_gait_set_terrain", "wbc_gait_terrain_check", "wbc_gait_terrain_kernel_info"]
-    assert header["wbc_gait_set_terrain"] == ("int", ["wbc_gait", "wbc_gait_terrain_params*", "wbc_terrain_profile*", "int", "uint8_t*", "double*"])
-    assert abi._prototype_mismatches(header, _lib.GAIT_TERRAIN_PROTOTYPES, _lib) == []
-    gaits = tgc._gait_header_prototypes()
-    assert len(gaits) == 8 and sorted(gaits) == sorted(_lib.GAIT_PROTOTYPES)
-    others = set(abi._header_prototypes()) | set(follow._ext_header_prototypes()) | set(gaits)
-    assert not set(header) & others
-    assert not set(_lib.GAIT_TERRAIN_PROTOTYPES) & (set(_lib.PROTOTYPES) | set(_lib.EXT_PROTOTYPES) | set(_lib.GAIT_PROTOTYPES))
-    L = _lib.lib()
-    for name, (restype, argtypes) in _lib.GAIT_TERRAIN_PROTOTYPES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
-    t = dict(_lib.GAIT_TERRAIN_PROTOTYPES)
-    res, args = t["wbc_gait_set_terrain"]
-    t["wbc_gait_set_terrain"] = (res, args[:3] + args[4:])                              # count dropped
-    bad = abi._prototype_mismatches(header, t, _lib)
-    assert len(bad) == 1 and bad[0].startswith("wbc_gait_set_terrain: 6 arguments in the header, 5"), bad
-    t = dict(_lib.GAIT_TERRAIN_PROTOTYPES)
-    del t["wbc_gait_terrain_kernel_info"]
-    assert abi._prototype_mismatches(header, t, _lib) == ["wbc_gait_terrain_kernel_info: declared in the headers, missing from the table"]
-    assert C.sizeof(_lib.WbcGaitTerrainParams) == 32
-    src = tmp_path / "gait_terrain.c"
-    src.write_text('#include "wbc_gait_terrain.h"\nint main(void) { return (int)sizeof(wbc_gait_terrain_params) - 32 + WBC_GAIT_BODY_LIFT '
-                   '+ WBC_GAIT_BODY_FIT - 1; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include_gait_terrain"), "-o",
-                    str(tmp_path / "gait_terrain"), str(src)], check=True, capture_output=True)
-    assert subprocess.run([str(tmp_path / "gait_terrain")]).returncode == 0
 
 
 def test_simulate_gait_terrain_arguments():

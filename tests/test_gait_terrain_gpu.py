@@ -1,4 +1,4 @@
-"""The gait planner's terrain on the MI355X (include_gait_terrain/wbc_gait_terrain.h; gait.GaitPlanner.set_terrain):
+"""The gait planner's terrain on the MI355X (include/wbc_gait_terrain.h; gait.GaitPlanner.set_terrain):
 wbc_gait_terrain_targets_kernel against the host instantiation of the same header (tests/host_gait_terrain.py) at the bars of
 tests/test_gait_terrain_cpu.py, malformed instances in every robot slot of a wavefront, the plain kernel still behind a handle without
 a terrain, the new kernel's resources, a terrain gait as the target source of wbc_ground_rollout against the same launches issued by

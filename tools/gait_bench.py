@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Measurements of the gait planner (include_gait/wbc_gait.h) for profiles/r13/gait.md and of its terrain
-(include_gait_terrain/wbc_gait_terrain.h) for profiles/r14/gait_terrain.md.
+"""Measurements of the gait planner (include/wbc_gait.h) for profiles/r13/gait.md and of its terrain
+(include/wbc_gait_terrain.h) for profiles/r14/gait_terrain.md.
 
     python tools/gait_bench.py kernel [--n 4096] [--bursts 30] [--burst 20]
     python tools/gait_bench.py loop --source traj|gait|gait_terrain|gait_follow [--n 4096] [--steps 300] [--repeats 5]

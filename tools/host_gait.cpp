@@ -4,7 +4,7 @@
 // library never calls it.
 #include <math.h>
 #include <stdint.h>
-#include "../include_gait/wbc_gait.h"
+#include "../include/wbc_gait.h"
 #include "../quadruped_drake_amd/csrc/wbc_gait.hpp"
 
 using namespace wbc;
@@ -44,7 +44,7 @@ int host_gait_batch(const wbc_gait_params* params, const wbc_gait_stride* stride
   return 0;
 }
 
-// The same with a terrain (include_gait_terrain/wbc_gait_terrain.h): + wbc_gait_set_terrain with host pointers.  Returns -2 on what
+// The same with a terrain (include/wbc_gait_terrain.h): + wbc_gait_set_terrain with host pointers.  Returns -2 on what
 // wbc_gait_terrain_check refuses in the parameters, -3 on a profile wbc_terrain_check refuses, -4 on parameters that do not fit the gait.
 int host_gait_terrain_batch(const wbc_gait_params* params, const wbc_gait_stride* strides, int count, const wbc_gait_terrain_params* tparams,
                             const wbc_terrain_profile* profiles, int tcount, int n, int ld, const double* time, const double* cmd,
