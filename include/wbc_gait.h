@@ -58,7 +58,9 @@
  *   are not moved away from edges.  With one set, the footholds keep clear of the steep pieces and the swing clears what lies between
  *   them: that header has the law and its own limits.  The law is a function of the time and the command
  *   arrays alone: a caller may rewrite cmd, gait_id, stride_scale or start between calls, and the body pose and the footholds then
- *   jump -- there is no blended transition.  The persistent wbc_rollout (wbc.h) takes no gait: its lookup is part of the tick kernels.
+ *   jump.  A command that changes along the way, with a blended transition and inside a rollout too, is a schedule
+ *   (include_gait_schedule/wbc_gait_schedule.h: up to seven switches per instance, joined by smooth turns); the stride and its scale
+ *   still hold for the whole run.  The persistent wbc_rollout (wbc.h) takes no gait: its lookup is part of the tick kernels.
  *
  * Rollouts.  While a gait is set on a plant handle (wbc_ground_set_gait, wbc_plant_set_gait), wbc_ground_rollout / wbc_plant_rollout
  * take every tick's targets and contact_mask from wbc_gait_targets instead of wbc_traj_lookup, and `traj` may be NULL: the order is

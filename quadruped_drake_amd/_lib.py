@@ -150,6 +150,13 @@ PROTOTYPES = {
     "wbc_gait_terrain_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
 }
 SYMBOLS = list(PROTOTYPES)
+# include_gait_schedule/wbc_gait_schedule.h: the gait planner's command schedules, a header in its own directory.  lib() binds these
+# when the library has them (tests/test_gait_schedule_cpu.py lays the rows beside that header's prototypes).
+PROTOTYPES_SCHEDULE = {
+    "wbc_gait_set_schedule": (_I, [_P, _P, _I, _I, _D, _P, _P, _P]),
+    "wbc_gait_clear_schedule": (_I, [_P]),
+    "wbc_gait_schedule_kernel_info": (_I, [_P, _I, _IP, _IP, _IP, _IP]),
+}
 # the names newer than the oldest kernel build still timed against (A/B timing: WBC_HIP_LIB; tools/qt.py --lib): the statistics
 # exchange, the follow law, the gait planner and its terrain
 _NEWER = ("wbc_stats_pack", "wbc_stats_reduce", "wbc_ground_follow_targets", "wbc_ground_set_follow", "wbc_ground_follow_kernel_info",
@@ -183,6 +190,10 @@ def lib():
         l = C.CDLL(LIB_PATH)
         for name, (restype, argtypes) in PROTOTYPES.items():
             if not (name in _MAY_LACK and not hasattr(l, name)):
+                fn = getattr(l, name)
+                fn.restype, fn.argtypes = restype, argtypes
+        for name, (restype, argtypes) in PROTOTYPES_SCHEDULE.items():
+            if hasattr(l, name):
                 fn = getattr(l, name)
                 fn.restype, fn.argtypes = restype, argtypes
         _lib = l

@@ -10,6 +10,10 @@
 // the law: the terrain table is staged in LDS beside the stride table, each lane puts its foot's two footholds on the terrain and
 // raises its swing over the knots between them, and the ground height under each foot and its two rates go round the quad by
 // wbc_quad.hpp's broadcasts for the body rows.  A handle with no terrain launches wbc_gait_targets_kernel, whose code is untouched.
+//
+// Command schedules (include_gait_schedule/wbc_gait_schedule.h) live in wbc_gait_schedule.hip, kernels and entry points: a translation
+// unit of their own, so that this one's device code stays what it was.  The handle here keeps that file's state behind one pointer
+// and hands a launch over to it while a schedule is set (wbc_gait_schedule_dev.hpp).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -19,6 +23,7 @@
 #include "../../include/wbc_gait.h"
 #include "../../include/wbc_gait_terrain.h"
 #include "wbc_gait.hpp"
+#include "wbc_gait_schedule_dev.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
 
@@ -145,6 +150,7 @@ struct wbc_gait_s {
   const double* start;
   double* d_terrain;       // the packed terrain table, GAIT_TERRAIN_DOUBLES doubles, allocated by the first wbc_gait_set_terrain
   GaitTerrainArgs terrain; // count == 0: no terrain, the plain kernel
+  wbc::GaitScheduleState* schedule;   // wbc_gait_schedule.hip's; nullptr until the first wbc_gait_set_schedule
 };
 
 extern "C" {
@@ -168,17 +174,19 @@ int wbc_gait_create(const wbc_gait_params* params, const wbc_gait_stride* stride
   g->cmd = nullptr; g->gait_id = nullptr; g->scale = nullptr; g->start = nullptr;
   g->d_terrain = nullptr;
   g->terrain = GaitTerrainArgs{};
+  g->schedule = nullptr;
   *out = g;
   return 0;
 }
 
 int wbc_gait_destroy(wbc_gait g) {
   if (!g) return 0;
-  if (g->d_table || g->d_terrain) {
+  if (g->d_table || g->d_terrain || g->schedule) {
     wbc::DeviceGuard device_guard_(g->device);
     (void)hipDeviceSynchronize();   // a launch still reading the tables
     if (g->d_table) (void)hipFree(g->d_table);
     if (g->d_terrain) (void)hipFree(g->d_terrain);
+    wbc::gait_schedule_free(g->schedule);
   }
   delete g;
   return 0;
@@ -207,8 +215,17 @@ int wbc_gait_targets(wbc_gait g, void* hip_stream, int n, int ld, const double* 
   const int rc = wbc::plant_check_batch("wbc_gait_targets", g, "gait", n, ld, time && targets && contact_mask, "time, targets and contact_mask");
   if (rc) return rc;
   if (!g->cmd || !g->d_table) return wbc::misuse("wbc_gait_targets: wbc_gait_set_commands has not been called on this handle");
+  if (wbc::gait_schedule_on(g->schedule) && n > g->schedule->args.n)
+    return wbc::misuse("wbc_gait_targets: n is larger than the n of the handle's wbc_gait_set_schedule");
   if (n == 0) return 0;
   WBC_ON_DEVICE(g->device, wbc::fail);
+  if (wbc::gait_schedule_on(g->schedule)) {
+    wbc::GaitLaunch L;
+    L.n = n; L.ld = ld; L.count = g->count; L.table = g->d_table; L.time = time; L.cmd = g->cmd; L.gait_id = g->gait_id;
+    L.scale = g->scale; L.start = g->start; L.targets = targets; L.mask = contact_mask;
+    L.tcount = g->terrain.count; L.ttable = g->terrain.table; L.tid = g->terrain.id; L.tscale = g->terrain.scale;
+    return wbc::gait_schedule_launch(g->schedule, hip_stream, L);
+  }
   GaitArgs a;
   a.n = n; a.ld = ld; a.count = g->count; a.table = g->d_table; a.time = time; a.cmd = g->cmd; a.gait_id = g->gait_id;
   a.scale = g->scale; a.start = g->start; a.targets = targets; a.mask = contact_mask;
@@ -222,6 +239,13 @@ int wbc_gait_targets(wbc_gait g, void* hip_stream, int n, int ld, const double* 
 
 // internal (not in include/wbc_gait.h): the handle's device, for the plants' wbc_*_set_gait
 int wbc_gait_device_(wbc_gait g) { return g->device; }
+
+// internal: what wbc_gait_schedule.hip needs of a handle -- its device, the cmd and start of wbc_gait_set_commands (cmd NULL: none
+// yet) and the slot that keeps that file's state
+int wbc_gait_schedule_slot_(wbc_gait g, int* device, const double** cmd, const double** start, wbc::GaitScheduleState*** slot) {
+  *device = g->device; *cmd = g->d_table ? g->cmd : nullptr; *start = g->start; *slot = &g->schedule;
+  return 0;
+}
 
 int wbc_gait_kernel_info(wbc_gait g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
   if (!g) return wbc::misuse("wbc_gait_kernel_info: null gait handle");

@@ -1,5 +1,6 @@
 // wbc_gait.hpp -- the gait planner's law (include/wbc_gait.h, "The law"; product code): its one text, instantiated by
-// wbc_gait_targets_kernel (wbc_gait.hip, a quad of lanes per robot, one foot per lane) and by tools/host_gait.cpp.
+// wbc_gait_targets_kernel (wbc_gait.hip, a quad of lanes per robot, one foot per lane), by the kernels of wbc_gait_schedule.hip (the
+// SCHEDULE instantiations: "command schedules" below) and by tools/host_gait.cpp.
 //
 // The host packs the parameters and every stride into one table of doubles (gait_pack): per (foot, phase) the bounds of the run the
 // phase lies in, relative to the start of the stride in progress, and for a swing run the bounds of the stance runs before and after
@@ -286,24 +287,187 @@ WBC_HD double gait_apex(const double* ter, const GaitGround& G, double swing_hei
   return fmin(ter[2], swing_height + m);
 }
 
+// ---------------------------------------------------------------- command schedules (include_gait_schedule/wbc_gait_schedule.h)
+// wbc_gait_set_schedule resolves every instance's switches once (gait_schedule_resolve, one thread per instance) into GAIT_KNOT_ROWS
+// rows per switch of a buffer [7 * GAIT_KNOT_ROWS][ld]; the SCHEDULE instantiations of gait_foot and gait_body then find a path
+// parameter's segment by seven compares and read that switch's rows only (gait_schedule_pose).  Rows of switch j (0-based):
+//   [0] Theta_j: +inf from the instance's m on; NaN in switch 0: the instance's schedule is invalid
+//   [1 .. 3] S_j = (x, y, psi)     [4 .. 6] c_j = (cx, cy, omega)
+//   [7 .. 12], [13 .. 18], [19 .. 24]  the blend's quintics of x, y and psi: q0, V0, A0 / 2, k3, k4, k5
+constexpr int GAIT_KNOT_ROWS = 25;
+constexpr int GAIT_MAX_SWITCHES = 7;
+constexpr int GAIT_SCHEDULE_ROWS = GAIT_MAX_SWITCHES * GAIT_KNOT_ROWS;
+
+// the quintic's six coefficients from value, V = beta q' and A = beta^2 q'' at its two ends
+WBC_HD void gait_quintic(double q0, double V0, double A0, double q1, double V1, double A1, double* k, size_t ld) {
+  const double D = q1 - q0 - V0 - 0.5 * A0, DV = V1 - V0 - A0, DA = A1 - A0;
+  k[0] = q0; k[ld] = V0; k[2 * ld] = 0.5 * A0;
+  k[3 * ld] = 10.0 * D - 4.0 * DV + 0.5 * DA;
+  k[4 * ld] = 7.0 * DV - 15.0 * D - DA;
+  k[5 * ld] = 6.0 * D - 3.0 * DV + 0.5 * DA;
+}
+
+// One instance's m switches -> its rows.  when and cmds point at the instance's column of when [7][ld] and cmds [21][ld] (rows from m
+// on are not read), knots at its column of the buffer, whose leading dimension is ldk.
+WBC_HD void gait_schedule_resolve(const GaitIn& in, double beta, int m, const double* when, const double* cmds, size_t ld, double* knots,
+                                  size_t ldk) {
+  bool bad = m > GAIT_MAX_SWITCHES;
+  GaitIn seg = in;               // the arc of the segment before the switch: its start and command
+  double org = 0.0;              // ... and the path parameter at which it starts
+  double least = 0.0;            // what the next Theta must reach
+  WBC_GAIT_UNROLL
+  for (int j = 0; j < GAIT_MAX_SWITCHES; j++) {
+    double* k = knots + (size_t)(j * GAIT_KNOT_ROWS) * ldk;
+    if (j < m) {
+      const double Th = when[(size_t)j * ld];
+      const double cx = cmds[(size_t)(3 * j) * ld], cy = cmds[(size_t)(3 * j + 1) * ld], w = cmds[(size_t)(3 * j + 2) * ld];
+      bad |= not_finite(Th) | not_finite(cx) | not_finite(cy) | not_finite(w) | !(Th >= least);
+      least = Th + beta;
+      double xE, yE, cE, sE, sS, cS;
+      const double tl = Th - org;
+      gait_pose(seg, tl, xE, yE, cE, sE);
+      const double psiE = seg.psi0 + seg.w * tl;
+      const double psiS = psiE + beta * (0.5 * (seg.w + w));
+      wbc_sincos(psiS, sS, cS);
+      const double ux = cE * seg.cx - sE * seg.cy, uy = sE * seg.cx + cE * seg.cy;   // Rz(psi_E) c_j-1
+      const double vx = cS * cx - sS * cy, vy = sS * cx + cS * cy;                   // Rz(psi_S) c_j
+      const double xS = xE + (0.5 * beta) * (ux + vx), yS = yE + (0.5 * beta) * (uy + vy);
+      const double bb = beta * beta;
+      k[0] = Th; k[ldk] = xS; k[2 * ldk] = yS; k[3 * ldk] = psiS; k[4 * ldk] = cx; k[5 * ldk] = cy; k[6 * ldk] = w;
+      gait_quintic(xE, beta * ux, bb * (0.0 - seg.w * uy), xS, beta * vx, bb * (0.0 - w * vy), k + 7 * ldk, ldk);
+      gait_quintic(yE, beta * uy, bb * (seg.w * ux), yS, beta * vy, bb * (w * vx), k + 13 * ldk, ldk);
+      gait_quintic(psiE, beta * seg.w, 0.0, psiS, beta * w, 0.0, k + 19 * ldk, ldk);
+      seg.x0 = xS; seg.y0 = yS; seg.psi0 = psiS; seg.cx = cx; seg.cy = cy; seg.w = w;
+      org = least;
+    } else {
+      k[0] = INFINITY;
+      WBC_GAIT_UNROLL
+      for (int r = 1; r < GAIT_KNOT_ROWS; r++) k[(size_t)r * ldk] = 0.0;
+    }
+  }
+  if (bad) knots[0] = __builtin_nan("");
+}
+
+struct GaitSchedule {   // what an instance's pose evaluations share
+  const double* knots;  // the instance's column of the buffer
+  size_t ld;
+  double beta;
+  double when[GAIT_MAX_SWITCHES];
+  bool bad;
+};
+WBC_HD GaitSchedule gait_schedule_load(const double* knots, size_t ld, size_t i, double beta) {
+  GaitSchedule S;
+  S.knots = knots + i; S.ld = ld; S.beta = beta;
+  WBC_GAIT_UNROLL
+  for (int j = 0; j < GAIT_MAX_SWITCHES; j++) S.when[j] = S.knots[(size_t)(j * GAIT_KNOT_ROWS) * ld];
+  S.bad = S.when[0] != S.when[0];
+  return S;
+}
+
+struct GaitSegment {    // where a pose evaluation fell, for the body rows
+  GaitIn a;             // the segment's arc as an instance: its start and its command
+  double tl;            // ... and the arc parameter
+  bool blend;           // inside a blend window: psi and the theta-derivatives below hold
+  double psi, dx, dy, dpsi, ddx, ddy, ddpsi;
+};
+
+// q(u) of a quintic in the buffer (and, RATES, its first and second derivative in u)
+template <bool RATES>
+WBC_HD void gait_quintic_at(const double* k, size_t ld, double u, double& q, double& qd, double& qdd) {
+  const double k0 = k[0], k1 = k[ld], k2 = k[2 * ld], k3 = k[3 * ld], k4 = k[4 * ld], k5 = k[5 * ld];
+  q = k0 + u * (k1 + u * (k2 + u * (k3 + u * (k4 + u * k5))));
+  if constexpr (RATES) {
+    qd = k1 + u * (2.0 * k2 + u * (3.0 * k3 + u * (4.0 * k4 + u * (5.0 * k5))));
+    qdd = 2.0 * k2 + u * (6.0 * k3 + u * (12.0 * k4 + u * (20.0 * k5)));
+  }
+}
+
+// a b + c d where the instantiations under a schedule owe the plain ones' bits (wbc_gait_schedule.h, "Exact relation").  The device
+// build contracts such a sum into one fused multiply-add, and which of the two products it fuses follows the order the optimiser
+// left the operands in, kernel by kernel: under a schedule, where the yaw's sine and cosine arrive through the blend's branch, it
+// left them the other way round.  So there the choice is written down -- the plain kernels': a b fused, c d rounded.  (On the
+// host nothing is contracted, and the sum is the plain text.)  tests/test_gait_schedule_gpu.py holds the relation on the device.
+WBC_HD double gait_pinned_dot2(double a, double b, double c, double d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_fma(a, b, c * d);
+#else
+  return a * b + c * d;
+#endif
+}
+
+// gait_pose under a schedule: P(th).  Before Theta_1 it is gait_pose(in, th) itself, on the same bits.
+template <bool RATES>
+WBC_HD void gait_schedule_pose(const GaitIn& in, const GaitSchedule& S, double th, double& x, double& y, double& cpsi, double& spsi,
+                               GaitSegment* seg) {
+  int s = 0;
+  WBC_GAIT_UNROLL
+  for (int j = 0; j < GAIT_MAX_SWITCHES; j++) s += (th >= S.when[j]) ? 1 : 0;
+  const bool first = s == 0;
+  const double* k = S.knots + (size_t)((first ? 0 : s - 1) * GAIT_KNOT_ROWS) * S.ld;
+  const double Th = k[0];
+  GaitIn a = in;
+  a.x0 = first ? in.x0 : k[S.ld]; a.y0 = first ? in.y0 : k[2 * S.ld]; a.psi0 = first ? in.psi0 : k[3 * S.ld];
+  a.cx = first ? in.cx : k[4 * S.ld]; a.cy = first ? in.cy : k[5 * S.ld]; a.w = first ? in.w : k[6 * S.ld];
+  const double d = th - Th;
+  const double tl = first ? th : d - S.beta;
+  const bool blend = !first & (d < S.beta);
+  gait_pose(a, tl, x, y, cpsi, spsi);
+  if constexpr (RATES) { seg->a = a; seg->tl = tl; seg->blend = blend; }
+  if (blend) {
+    const double u = d / S.beta;
+    double psi, r1, r2, r3, r4, r5, r6;
+    gait_quintic_at<RATES>(k + 7 * S.ld, S.ld, u, x, r1, r2);
+    gait_quintic_at<RATES>(k + 13 * S.ld, S.ld, u, y, r3, r4);
+    gait_quintic_at<RATES>(k + 19 * S.ld, S.ld, u, psi, r5, r6);
+    wbc_sincos(psi, spsi, cpsi);
+    if constexpr (RATES) {
+      const double ib = 1.0 / S.beta, ibb = ib * ib;
+      seg->psi = psi;
+      seg->dx = r1 * ib; seg->ddx = r2 * ibb;
+      seg->dy = r3 * ib; seg->ddy = r4 * ibb;
+      seg->dpsi = r5 * ib; seg->ddpsi = r6 * ibb;
+    }
+  }
+}
+
+// what the body rows take from a pose evaluation: under a schedule the segment's, otherwise the instance's own
+template <bool SCHEDULE> WBC_HD const GaitIn& gait_arc(const GaitSegment& g, const GaitIn& in) {
+  if constexpr (SCHEDULE) return g.a;
+  else return in;
+}
+template <bool SCHEDULE> WBC_HD double gait_arc(const GaitSegment& g, double th) {
+  if constexpr (SCHEDULE) return g.tl;
+  else return th;
+}
+
 // the 18 body rows.  TERRAIN: ter the terrain table and gr[3 f + d] the ground height under foot f (d = 0) and its first and second
-// time derivatives, as gait_foot hands them out.
-template <bool TERRAIN = false>
+// time derivatives, as gait_foot hands them out.  SCHEDULE: S the instance's schedule.
+template <bool TERRAIN = false, bool SCHEDULE = false>
 WBC_HD void gait_body(const double* table, const GaitIn& in, const GaitClock& c, double* b, const double* ter = nullptr,
-                      const double* gr = nullptr) {
+                      const double* gr = nullptr, const GaitSchedule* S = nullptr) {
   double th, thd, thdd, x, y, cp, sp;
   gait_theta(table[10], c.pre ? 0.0 : c.tau, th, thd, thdd);
   th = c.pre ? 0.0 : th; thd = c.pre ? 0.0 : thd; thdd = c.pre ? 0.0 : thdd;
-  gait_pose(in, th, x, y, cp, sp);
-  const double vx = cp * in.cx - sp * in.cy, vy = sp * in.cx + cp * in.cy;   // Rz(psi) c
-  const double cen = thd * thd * in.w;
+  [[maybe_unused]] GaitSegment g;
+  if constexpr (SCHEDULE) gait_schedule_pose<true>(in, *S, th, x, y, cp, sp, &g);
+  else gait_pose(in, th, x, y, cp, sp);
+  const GaitIn& e = gait_arc<SCHEDULE>(g, in);          // the arc the pose lies on, and its parameter: without a schedule, in and th
+  const double tl = gait_arc<SCHEDULE>(g, th);
+  const double vx = cp * e.cx - sp * e.cy, vy = sp * e.cx + cp * e.cy;   // Rz(psi) c
+  const double cen = thd * thd * e.w;
   const double nan = __builtin_nan("");
   b[0] = x; b[1] = y; b[2] = table[8];
   b[3] = thd * vx; b[4] = thd * vy; b[5] = 0.0;
   b[6] = thdd * vx - cen * vy; b[7] = thdd * vy + cen * vx; b[8] = 0.0;
-  b[9] = 0.0; b[10] = 0.0; b[11] = in.psi0 + in.w * th;
-  b[12] = 0.0; b[13] = 0.0; b[14] = in.w * thd;
-  b[15] = 0.0; b[16] = 0.0; b[17] = in.w * thdd;
+  b[9] = 0.0; b[10] = 0.0; b[11] = e.psi0 + e.w * tl;
+  b[12] = 0.0; b[13] = 0.0; b[14] = e.w * thd;
+  b[15] = 0.0; b[16] = 0.0; b[17] = e.w * thdd;
+  if constexpr (SCHEDULE) {                              // inside a blend window: the chain rule on the quintics
+    const double tt = thd * thd;
+    b[3] = g.blend ? thd * g.dx : b[3]; b[4] = g.blend ? thd * g.dy : b[4];
+    b[6] = g.blend ? thdd * g.dx + tt * g.ddx : b[6]; b[7] = g.blend ? thdd * g.dy + tt * g.ddy : b[7];
+    b[11] = g.blend ? g.psi : b[11]; b[14] = g.blend ? thd * g.dpsi : b[14]; b[17] = g.blend ? thdd * g.dpsi + tt * g.ddpsi : b[17];
+  }
   if constexpr (TERRAIN) {
     double m[3], P[3], Q[3];
     WBC_GAIT_UNROLL
@@ -325,9 +489,10 @@ WBC_HD void gait_body(const double* table, const GaitIn& in, const GaitClock& c,
 
 // the 9 rows of foot f; run (optional, for the tests): the start a of the run the foot is in, and u = (tau - a) / D as the rows use it.
 // TERRAIN: ter the terrain table, G the instance's ground; gr[3] <- the ground height under the foot and its two time derivatives.
-template <bool TERRAIN = false>
+// SCHEDULE: S the instance's schedule.
+template <bool TERRAIN = false, bool SCHEDULE = false>
 WBC_HD void gait_foot(const double* table, const GaitIn& in, const GaitClock& c, int f, double* o, double* run = nullptr,
-                      const double* ter = nullptr, const GaitGround* G = nullptr, double* gr = nullptr) {
+                      const double* ter = nullptr, const GaitGround* G = nullptr, double* gr = nullptr, const GaitSchedule* S = nullptr) {
   const double* e = c.stride + 12 + 6 * (8 * f + c.phase);
   const double sx = table[2 * f], sy = table[2 * f + 1], ramp = table[10];
   double a, b, pa, pb, na, nb;
@@ -347,9 +512,11 @@ WBC_HD void gait_foot(const double* table, const GaitIn& in, const GaitClock& c,
     double th, thd, thdd, x, y, cp, sp;
     gait_theta(ramp, fmax(0.5 * (lo + hi), 0.0), th, thd, thdd);
     th = (c.pre | (lo <= 0.0)) ? 0.0 : th;
-    gait_pose(in, th, x, y, cp, sp);
+    if constexpr (SCHEDULE) gait_schedule_pose<false>(in, *S, th, x, y, cp, sp, nullptr);
+    else gait_pose(in, th, x, y, cp, sp);
     F[h][0] = x + (cp * sx - sp * sy);
-    F[h][1] = y + (sp * sx + cp * sy);
+    if constexpr (SCHEDULE) F[h][1] = y + gait_pinned_dot2(sp, sx, cp, sy);
+    else F[h][1] = y + (sp * sx + cp * sy);
     if constexpr (TERRAIN) gait_foothold_on(ter, *G, c.pre | (lo <= 0.0), F[h][0], F[h][1], Fs[h], Fz[h]);
   }
   const double D = b - a, u = (c.tau - a) / D, w = 1.0 - u, uw = u * w;

@@ -8,6 +8,8 @@ and its own stride period, and no table of samples.  `plant.closed_loop` takes a
 `GaitPlanner.set_terrain` gives the planner the plant's terrain (include/wbc_gait_terrain.h): its targets are then the
 finished targets on that ground -- footholds off the risers, swings that clear the knots, a body that follows the feet -- and no
 follow pass runs after them.
+`GaitPlanner.set_schedule` steers it (include_gait_schedule/wbc_gait_schedule.h): every robot walks its own sequence of commands,
+switched at its own times and joined by smooth turns -- up to a kerb and along it, a square, to a stop, into reverse.
 Torch tensors and torch's current stream, as in controller.py and plant.py.
 """
 import ctypes as C
@@ -38,6 +40,39 @@ STRIDES = {
     "limp": ((0.1, 0.2, 0.1, 0.1, 0.2, 0.1), (_Bb, _BB, _IP, _Bb, _BB, _IP)),                       # :347-366 GetStrideLimp
 }
 MAX_STRIDES, MAX_PHASES = 16, 8   # WBC_GAIT_MAX_STRIDES, WBC_GAIT_MAX_PHASES
+MAX_SWITCHES = 7                  # WBC_GAIT_MAX_SWITCHES
+
+
+def path_parameter(ramp_time, t):
+    """theta(t) of include/wbc_gait.h: the body's path parameter at t >= 0 [s after wait_time], numpy"""
+    t = np.asarray(t, dtype=np.float64)
+    if ramp_time > 0:
+        x = np.minimum(t / ramp_time, 1.0)
+        return np.where(t < ramp_time, ramp_time * (2.5 * x**4 - 3.0 * x**5 + x**6), t - 0.5 * ramp_time)
+    return t.copy()
+
+
+def schedule_arrays(times, cmds, n, ramp_time):
+    """(nswitch [n] uint8, when [7, n], cmds [21, n]) as wbc_gait_set_schedule takes them, numpy.  times: [M] or [M, n] seconds after
+    wait_time, M <= 7, +inf from a robot's last switch on; cmds: [M, 3] or [M, 3, n] = (vx, vy, yaw rate) from each switch on."""
+    times, cmds = np.asarray(times, dtype=np.float64), np.asarray(cmds, dtype=np.float64)
+    if times.ndim == 1:
+        times = np.repeat(times[:, None], n, axis=1)
+    if cmds.ndim == 2:
+        cmds = np.repeat(cmds[:, :, None], n, axis=2)
+    m = times.shape[0]
+    if times.ndim != 2 or m > MAX_SWITCHES or times.shape[1] != n or cmds.shape != (m, 3, n):
+        raise ValueError("set_schedule: times [M] or [M, N] and cmds [M, 3] or [M, 3, N] with M <= %d and N = %d" % (MAX_SWITCHES, n))
+    used = times < np.inf
+    if np.isnan(times).any() or (used[1:] & ~used[:-1]).any():
+        raise ValueError("set_schedule: times are numbers, +inf from a robot's last switch on")
+    if (times[used] < ramp_time).any():
+        raise ValueError("set_schedule: a switch must lie at or after ramp_time (%g s)" % ramp_time)
+    when = np.full((MAX_SWITCHES, n), np.inf)
+    when[:m] = np.where(used, path_parameter(ramp_time, np.where(used, times, ramp_time)), np.inf)
+    c = np.zeros((3 * MAX_SWITCHES, n))
+    c[:3 * m] = np.where(used[:, None, :], cmds, 0.0).reshape(3 * m, n)
+    return used.sum(0).astype(np.uint8), when, c
 
 
 def stride(spec):
@@ -111,6 +146,7 @@ class GaitPlanner:
         self._n = None
         self._keep = None
         self._terrain = None
+        self._schedule = None
         h = C.c_void_p()
         _lib.check(self._L.wbc_gait_create(C.byref(self.params), c_strides(self.strides), len(self.strides), self.device, C.byref(h)))
         self._h = h
@@ -129,6 +165,38 @@ class GaitPlanner:
         p0 = _lib.dev_ptr(start, 3, n, torch.float64, "start", d, "the planner", True)
         _lib.check(self._L.wbc_gait_set_commands(self._h, pc, pg, ps, p0))
         self._n, self._keep = n, (cmd, gait_id, stride_scale, start)
+
+    def set_schedule(self, times, cmds, blend=0.5):
+        """Steer the planner (include_gait_schedule/wbc_gait_schedule.h): from times[j] [s after wait_time] on a robot walks cmds[j]
+        instead of the command before it, the first being set_commands' cmd.  times: [M] or [M, N], M <= 7, each at or after
+        ramp_time, +inf from a robot's last switch on; cmds: [M, 3] or [M, 3, N]; numpy or lists, one column per robot or one for
+        all.  blend [s of steady walking]: the length of the smooth turn after a switch, which must end before the next switch
+        (a robot whose switches are closer gets NaN targets).  Needs set_commands, and is called again after cmd or start are
+        rewritten.  Synchronises torch's current stream."""
+        import torch
+        if self._n is None:
+            raise ValueError("GaitPlanner.set_schedule: set_commands first")
+        n, d = self._n, self.device
+        m, when, c = schedule_arrays(times, cmds, n, self.params.ramp_time)
+        dev = "cuda:%d" % d
+        tm, tw, tc = (torch.tensor(a, device=dev) for a in (m, when, c))
+        s = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
+        _lib.check(self._L.wbc_gait_set_schedule(self._h, s, n, n, float(blend), C.c_void_p(tm.data_ptr()), C.c_void_p(tw.data_ptr()),
+                                                 C.c_void_p(tc.data_ptr())))
+        self._schedule = (m, when, c, float(blend))
+
+    def clear_schedule(self):
+        """One command per robot again: the kernels a planner without a schedule launches."""
+        _lib.check(self._L.wbc_gait_clear_schedule(self._h))
+        self._schedule = None
+
+    @property
+    def has_schedule(self):
+        return getattr(self, "_schedule", None) is not None
+
+    def schedule_kernel_info(self, terrain=False):
+        """kernel_info() of the kernel that runs while a schedule is set, without or with a terrain."""
+        return _lib.kernel_info(lambda h, *out: self._L.wbc_gait_schedule_kernel_info(h, int(bool(terrain)), *out), self._h)
 
     def targets(self, time, out=None):
         """-> (targets [54, N] float64, contact_mask [N] uint8) at time [N] float64; out: such a pair to write into.  Asynchronous on
@@ -201,6 +269,7 @@ class GaitPlanner:
             self._h = None
             self._keep = None
             self._terrain = None
+            self._schedule = None
 
     def __del__(self):
         try:

@@ -25,6 +25,9 @@ WALK: gait.GaitPlanner computes each tick's targets on the device from a velocit
 (gait.STRIDES); S scales the stride's durations and defaults to 0.5: ID at TOWR's own 1.0 s trot falls when it steps in place, walks
 backwards or climbs a slope of grade 0.2, and walks all of them at half that period (profiles/r13/gait.md, gait_sweep.md).  With
 `--plant ground` the result line also has the mean and the worst distance of the trunks from their planned (x, y).
+`--cmd-schedule "T:VX,VY,WZ;..." [--cmd-blend B]` (with `--planner gait`) steers every robot: from T seconds on it walks VX,VY,WZ, with a
+smooth turn of length B (default 0.5) after each of up to seven switches (include_gait_schedule/wbc_gait_schedule.h); `--cmd-spread`
+spreads the first command only.
 `--gait-terrain lift|fit` (with `--planner gait` and `--terrain`; default `off`; excludes `--follow`) gives the plant's terrain to the
 planner (include/wbc_gait_terrain.h): footholds on the surface and off the risers, swings that clear what lies between
 their footholds, a body that follows the feet (`fit`: also in pitch and roll).  That is what walks a kerb of 0.1 m."""
@@ -62,6 +65,9 @@ def parse(argv=None):
     ap.add_argument("--terrain", default=None, help="--plant ground only: NAME[:PARAM], e.g. slope:0.2 (flat, slope, ramp_step, stairs, ridge)")
     ap.add_argument("--follow", default="off", choices=("off", "lift", "fit"),
                     help="--terrain only: make the targets follow the ground (lift: heights; fit: heights and the trunk's attitude)")
+    ap.add_argument("--cmd-schedule", default=None,
+                    help="gait planner: T:VX,VY,WZ;... -- from T [s] on walk VX,VY,WZ; up to 7 switches, at rising times from 0.5 s (the ramp) on")
+    ap.add_argument("--cmd-blend", type=float, default=0.5, help="--cmd-schedule: the length of the smooth turn after a switch [s]")
     ap.add_argument("--gait-terrain", default="off", choices=("off", "lift", "fit"),
                     help="--planner gait with --terrain only: the planner walks ON the terrain (lift: body height; fit: and its attitude)")
     ap.add_argument("--device", type=int, default=0)
@@ -87,6 +93,19 @@ def parse(argv=None):
             setattr(a, name, val)
         if not (a.stride_scale > 0 and np.isfinite(a.stride_scale)):
             ap.error("--stride-scale must be positive and finite")
+        if a.cmd_schedule is not None:
+            try:
+                items = [(float(t), tuple(float(x) for x in c.split(","))) for t, c in (item.split(":") for item in a.cmd_schedule.split(";"))]
+            except ValueError:
+                items = []
+            ok = 1 <= len(items) <= gait.MAX_SWITCHES and all(len(c) == 3 and np.isfinite(t) and all(np.isfinite(c)) for t, c in items)
+            if not ok or not (a.cmd_blend >= 0 and np.isfinite(a.cmd_blend)):
+                ap.error("--cmd-schedule: expected 1 .. 7 items T:VX,VY,WZ separated by ';', and --cmd-blend >= 0")
+            if items[0][0] < 0.5 or any(t1 < t0 + a.cmd_blend for (t0, _), (t1, _) in zip(items, items[1:])):
+                ap.error("--cmd-schedule: the first switch at 0.5 s (the ramp) or later, every other at least --cmd-blend after the one before")
+            a.cmd_schedule = items
+    if a.cmd_schedule is not None and a.planner != "gait":
+        ap.error("--cmd-schedule needs --planner gait")
     if a.terrain is not None:
         if a.plant != "ground":
             ap.error("--terrain needs --plant ground")
@@ -159,6 +178,8 @@ def run(a):
     if cmd is not None:                 # the plan starts where the trunk stands (on a terrain: off the origin, along the normal)
         traj.set_commands(torch.tensor(cmd, device=dev), stride_scale=torch.full((a.n,), a.stride_scale, dtype=torch.float64, device=dev),
                           start=torch.tensor(np.stack([q0[4], q0[5], np.zeros(a.n)]), device=dev))
+        if a.cmd_schedule is not None:
+            traj.set_schedule([t for t, _ in a.cmd_schedule], [c for _, c in a.cmd_schedule], blend=a.cmd_blend)
     steps = int(round(a.sim_time / a.dt))
     ts, mets = [], []
     ctrl.stats(reset=True)
@@ -205,6 +226,8 @@ def main(argv=None):
         if "plan_offset" in r:
             extra.update(gait=a.gait, cmd=list(a.cmd), cmd_spread=list(a.cmd_spread), stride_scale=a.stride_scale,
                          plan_offset_mean=r["plan_offset"]["mean"], plan_offset_worst=r["plan_offset"]["worst"])
+            if a.cmd_schedule is not None:
+                extra.update(cmd_schedule=[[t] + list(c) for t, c in a.cmd_schedule], cmd_blend=a.cmd_blend)
     print(json.dumps({"control": a.control, "planner": a.planner, "scenario": a.scenario if a.planner == "basic" else a.gait if a.planner == "gait" else a.messages,
                       "n": a.n, "sim_time": a.sim_time, "dt": a.dt, "ticks": r["ticks"], "status_nonzero": r["status_nonzero"],
                       "ticks_per_second": r["ticks_per_second"], "active_set_iterations_mean": r["iters_mean"],

@@ -3,19 +3,22 @@
 (include/wbc_gait_terrain.h) for profiles/r14/gait_terrain.md.
 
     python tools/gait_bench.py kernel [--n 4096] [--bursts 30] [--burst 20]
-    python tools/gait_bench.py loop --source traj|gait|gait_terrain|gait_follow [--n 4096] [--steps 300] [--repeats 5]
+    python tools/gait_bench.py loop --source traj|gait|gait_terrain|gait_follow|gait_schedule [--n 4096] [--steps 300] [--repeats 5]
 
   kernel: device time per launch of wbc_gait_targets_kernel (a trot, per-instance commands, scales and starts, times spread over
     3 s) and of the target-lookup kernel beside it: HIP events around bursts of back-to-back launches after a warm-up, the median
     over the bursts.  A library with the gait's terrain also gets wbc_gait_terrain_targets_kernel timed in the same process: the same
-    planner on sixteen kerbs and stairs, each instance with its own profile and scale, FIT.
+    planner on sixteen kerbs and stairs, each instance with its own profile and scale, FIT.  A library with the command schedules
+    (include_gait_schedule/wbc_gait_schedule.h) also gets wbc_gait_schedule_targets_kernel and wbc_gait_schedule_terrain_targets_kernel
+    timed: the same planner, every instance with its own three switches inside the 3 s of sampled times, blend 0.5 -- and the plain
+    kernels again once the schedule is cleared.
   loop: time per 1 ms tick of wbc_ground_rollout at 16 substeps, MPTC, with the targets looked up in a recorded trot
     (tools/follow_bench.py's; `traj`: the launches the rollout issued before it could take a gait) or computed by the gait (`gait`:
     a trot at stride scale 0.5, commands over +-0.3 m/s and +-0.5 rad/s).  One figure per process; the caller runs them in turn.  A
     library from before the gait planner (WBC_HIP_LIB) is measured with `--source traj`, which calls nothing it lacks.
     `gait_terrain`: the plant on sixteen kerbs and stairs and the gait on the same terrain (one terrain kernel per tick);
     `gait_follow`: the same ground under the plain gait with the follow law in FIT after it (two kernels per tick), the path a
-    terrain gait replaces.
+    terrain gait replaces.  `gait_schedule`: `gait` steered by three switches per instance (one schedule kernel per tick).
 Both print one JSON line."""
 import argparse
 import json
@@ -54,6 +57,15 @@ def _terrains(n, seed=2):
     return profiles, tid, tsc
 
 
+def _schedule(p, n, seed=3):
+    """three switches per instance inside the 3 s of sampled times, blend 0.5"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    times = np.stack([rng.uniform(0.5, 0.8, n), rng.uniform(1.4, 1.7, n), rng.uniform(2.3, 2.6, n)])
+    cmds = np.stack([np.stack([rng.uniform(-0.3, 0.3, n), rng.uniform(-0.1, 0.1, n), rng.uniform(-0.5, 0.5, n)]) for _ in range(3)])
+    p.set_schedule(times, cmds, blend=0.5)
+
+
 def kernel(a):
     import numpy as np
     import torch
@@ -72,6 +84,18 @@ def kernel(a):
         res["gait_terrain"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
         p.clear_terrain()
         res["gait_after_clear"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
+    if hasattr(p._L, "wbc_gait_set_schedule"):
+        _schedule(p, a.n)
+        res["schedule_kernel"] = p.schedule_kernel_info()
+        res["gait_schedule"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
+        profiles, tid, tsc = _terrains(a.n)
+        p.set_terrain(profiles, terrain_id=tid, terrain_scale=tsc, body="fit")
+        res["schedule_terrain_kernel"] = p.schedule_kernel_info(terrain=True)
+        res["gait_schedule_terrain"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
+        p.clear_schedule()
+        res["gait_terrain_after_clear_schedule"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
+        p.clear_terrain()
+        res["gait_after_clear_schedule"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
     st_t = workloads.standing_targets("mini_cheetah", 1)[:, 0]
     K = 4000
     traj = TrunkTrajectory(np.arange(K) * 1e-3, np.tile(st_t, (K, 1)), np.full(K, 15, np.uint8), wait_time=0.0, device=0,
@@ -91,6 +115,8 @@ def loop(a):
     n, dt, dev = a.n, 1e-3, "cuda:0"
     if a.source.startswith("gait"):
         src = _planner(n)
+        if a.source == "gait_schedule":
+            _schedule(src, n)
     else:
         st_t = workloads.standing_targets("mini_cheetah", 1)[:, 0]
         K = 4000
@@ -136,7 +162,7 @@ def main():
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--bursts", type=int, default=30)
     ap.add_argument("--burst", type=int, default=20)
-    ap.add_argument("--source", default="traj", choices=("traj", "gait", "gait_terrain", "gait_follow"))
+    ap.add_argument("--source", default="traj", choices=("traj", "gait", "gait_terrain", "gait_follow", "gait_schedule"))
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()

@@ -76,4 +76,55 @@ int host_gait_terrain_batch(const wbc_gait_params* params, const wbc_gait_stride
   return 0;
 }
 
+// The same under command schedules (include_gait_schedule/wbc_gait_schedule.h): + wbc_gait_set_schedule with host pointers, on the plane
+// (tparams NULL) or on a terrain.  Returns -5 on null schedule arrays or a blend that is negative or not finite.  knots (optional,
+// [GAIT_SCHEDULE_ROWS][ld]): the resolved schedules, as the handle's buffer holds them.
+int host_gait_schedule_batch(const wbc_gait_params* params, const wbc_gait_stride* strides, int count, const wbc_gait_terrain_params* tparams,
+                             const wbc_terrain_profile* profiles, int tcount, int n, int ld, const double* time, const double* cmd,
+                             const uint8_t* gait_id, const double* stride_scale, const double* start, const uint8_t* terrain_id,
+                             const double* terrain_scale, double blend, const uint8_t* nswitch, const double* when, const double* cmds,
+                             double* targets, uint8_t* contact_mask, double* knots) {
+  if (gait_error(params, strides, count)) return -1;
+  if (!nswitch || !when || !cmds || !(blend >= 0.0) || not_finite(blend)) return -5;
+  double table[GAIT_TABLE_DOUBLES] = {0.0}, ter[GAIT_TERRAIN_DOUBLES] = {0.0};
+  gait_pack(params, strides, count, table);
+  if (tparams) {
+    if (gait_terrain_error(tparams)) return -2;
+    if (!profiles || tcount < 1 || tcount > TERRAIN_MAX_PROFILES) return -3;
+    for (int p = 0; p < tcount; p++)
+      if (terrain_profile_error(profiles[p].nk, profiles[p].x0, profiles[p].y0, profiles[p].yaw, profiles[p].s, profiles[p].h)) return -3;
+    if (gait_terrain_fit_error(tparams, table)) return -4;
+    gait_terrain_pack(tparams, table, profiles, tcount, ter);
+  }
+  double own[GAIT_SCHEDULE_ROWS];
+  for (int i = 0; i < n; i++) {
+    const GaitIn in = gait_load(time, cmd, gait_id, stride_scale, start, (size_t)ld, (size_t)i);
+    double* k = knots ? knots + i : own;
+    const size_t ldk = knots ? (size_t)ld : 1;
+    gait_schedule_resolve(in, blend, (int)nswitch[i], when + i, cmds + i, (size_t)ld, k, ldk);
+    const GaitSchedule S = gait_schedule_load(k, ldk, 0, blend);
+    GaitClock c = gait_clock(table, count, in);
+    double b[18], f[9], gr[12];
+    if (tparams) {
+      const GaitGround G = gait_ground(ter, tcount, terrain_id ? (int)terrain_id[i] : 0, terrain_scale ? terrain_scale[i] : 1.0);
+      gait_clock_spoil(c, G.bad | S.bad);
+      for (int l = 0; l < 4; l++) {
+        gait_foot<true, true>(table, in, c, l, f, nullptr, ter, &G, gr + 3 * l, &S);
+        for (int r = 0; r < 9; r++) targets[(size_t)(18 + 9 * l + r) * ld + i] = f[r];
+      }
+      gait_body<true, true>(table, in, c, b, ter, gr, &S);
+    } else {
+      gait_clock_spoil(c, S.bad);
+      for (int l = 0; l < 4; l++) {
+        gait_foot<false, true>(table, in, c, l, f, nullptr, nullptr, nullptr, nullptr, &S);
+        for (int r = 0; r < 9; r++) targets[(size_t)(18 + 9 * l + r) * ld + i] = f[r];
+      }
+      gait_body<false, true>(table, in, c, b, nullptr, nullptr, &S);
+    }
+    for (int r = 0; r < 18; r++) targets[(size_t)r * ld + i] = b[r];
+    contact_mask[i] = (uint8_t)c.mask;
+  }
+  return 0;
+}
+
 }  // extern "C"
