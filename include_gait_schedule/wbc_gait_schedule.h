@@ -41,8 +41,9 @@
  *   Exact relation.  An instance with m = 0 gets the bits of the law without a schedule, and so does any instance while all three
  *   of its pose evaluations lie before Theta_1.
  *
- *   The limits.  The stride and the stride scale do not change along the schedule; the schedule is a plan, not a feedback: it takes
- *   nothing from the measured state.  The persistent wbc_rollout (wbc.h) takes no gait.
+ *   The limits.  The stride and the stride scale do not change along the schedule; the schedule itself is a plan: it takes nothing
+ *   from the measured state.  What reacts to the measured trunk is a pass after it that shifts the footholds
+ *   (include_gait_feedback/wbc_gait_feedback.h), with or without a schedule.  The persistent wbc_rollout (wbc.h) takes no gait.
  *
  * Rollouts take the gait handle as their target source (wbc_gait.h), so a schedule set on it steers wbc_ground_rollout and
  * wbc_plant_rollout with no further call.

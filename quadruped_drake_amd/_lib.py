@@ -68,12 +68,17 @@ class WbcGaitTerrainParams(C.Structure):
     _fields_ = [("body_mode", C.c_int), ("max_grade", C.c_double), ("edge_margin", C.c_double), ("apex_max", C.c_double)]
 
 
+class WbcGaitFeedbackParams(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("k_v", "k_p", "d_max", "u_hold")]
+
+
 _P, _I, _D = C.c_void_p, C.c_int, C.c_double
 _IP, _FP, _HP = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_void_p)
 _MODEL, _PARAMS, _STATS = C.POINTER(WbcModel), C.POINTER(WbcParams), C.POINTER(WbcStats)
 _TRUNK, _ROBOT = C.POINTER(WbcTrunkState), C.POINTER(WbcRobotState)
 _PLANTP, _GROUNDP = C.POINTER(WbcPlantParams), C.POINTER(WbcGroundParams)
 _GAITP, _GAITS, _GAITTP = C.POINTER(WbcGaitParams), C.POINTER(WbcGaitStride), C.POINTER(WbcGaitTerrainParams)
+_GAITFP = C.POINTER(WbcGaitFeedbackParams)
 
 # name: (restype, argtypes) of every function the headers of include/ declare, one position per argument in the header's order
 # (tests/test_abi_cpu.py lays each row beside the header's prototype).  A handle, a stream and a device array are _P.
@@ -157,6 +162,16 @@ PROTOTYPES_SCHEDULE = {
     "wbc_gait_clear_schedule": (_I, [_P]),
     "wbc_gait_schedule_kernel_info": (_I, [_P, _I, _IP, _IP, _IP, _IP]),
 }
+# include_gait_feedback/wbc_gait_feedback.h: the gait planner's foot-placement feedback, likewise a header in its own directory, bound
+# when the library has the names (tests/test_gait_feedback_cpu.py lays the rows beside that header's prototypes)
+PROTOTYPES_FEEDBACK = {
+    "wbc_gait_feedback_check": (_I, [_GAITFP]),
+    "wbc_gait_feedback_params_default": (_I, [_GAITP, _GAITFP]),
+    "wbc_gait_set_feedback": (_I, [_P, _GAITFP, _I]),
+    "wbc_gait_clear_feedback": (_I, [_P]),
+    "wbc_gait_targets_measured": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "wbc_gait_feedback_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
+}
 # the names newer than the oldest kernel build still timed against (A/B timing: WBC_HIP_LIB; tools/qt.py --lib): the statistics
 # exchange, the follow law, the gait planner and its terrain
 _NEWER = ("wbc_stats_pack", "wbc_stats_reduce", "wbc_ground_follow_targets", "wbc_ground_set_follow", "wbc_ground_follow_kernel_info",
@@ -192,7 +207,7 @@ def lib():
             if not (name in _MAY_LACK and not hasattr(l, name)):
                 fn = getattr(l, name)
                 fn.restype, fn.argtypes = restype, argtypes
-        for name, (restype, argtypes) in PROTOTYPES_SCHEDULE.items():
+        for name, (restype, argtypes) in list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_FEEDBACK.items()):
             if hasattr(l, name):
                 fn = getattr(l, name)
                 fn.restype, fn.argtypes = restype, argtypes

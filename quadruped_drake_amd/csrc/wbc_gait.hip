@@ -14,6 +14,9 @@
 // Command schedules (include_gait_schedule/wbc_gait_schedule.h) live in wbc_gait_schedule.hip, kernels and entry points: a translation
 // unit of their own, so that this one's device code stays what it was.  The handle here keeps that file's state behind one pointer
 // and hands a launch over to it while a schedule is set (wbc_gait_schedule_dev.hpp).
+//
+// The foot-placement feedback (include_gait_feedback/wbc_gait_feedback.h) lives in wbc_gait_feedback.hip in the same way: its state
+// hangs off the handle by one pointer, and wbc_gait_targets knows nothing of it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -24,6 +27,7 @@
 #include "../../include/wbc_gait_terrain.h"
 #include "wbc_gait.hpp"
 #include "wbc_gait_schedule_dev.hpp"
+#include "wbc_gait_feedback.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
 
@@ -151,6 +155,7 @@ struct wbc_gait_s {
   double* d_terrain;       // the packed terrain table, GAIT_TERRAIN_DOUBLES doubles, allocated by the first wbc_gait_set_terrain
   GaitTerrainArgs terrain; // count == 0: no terrain, the plain kernel
   wbc::GaitScheduleState* schedule;   // wbc_gait_schedule.hip's; nullptr until the first wbc_gait_set_schedule
+  wbc::GaitFeedbackState* feedback;   // wbc_gait_feedback.hip's; nullptr unless wbc_gait_set_feedback holds
 };
 
 extern "C" {
@@ -175,18 +180,20 @@ int wbc_gait_create(const wbc_gait_params* params, const wbc_gait_stride* stride
   g->d_terrain = nullptr;
   g->terrain = GaitTerrainArgs{};
   g->schedule = nullptr;
+  g->feedback = nullptr;
   *out = g;
   return 0;
 }
 
 int wbc_gait_destroy(wbc_gait g) {
   if (!g) return 0;
-  if (g->d_table || g->d_terrain || g->schedule) {
+  if (g->d_table || g->d_terrain || g->schedule || g->feedback) {
     wbc::DeviceGuard device_guard_(g->device);
     (void)hipDeviceSynchronize();   // a launch still reading the tables
     if (g->d_table) (void)hipFree(g->d_table);
     if (g->d_terrain) (void)hipFree(g->d_terrain);
     wbc::gait_schedule_free(g->schedule);
+    wbc::gait_feedback_free(g->feedback);
   }
   delete g;
   return 0;
@@ -246,6 +253,19 @@ int wbc_gait_schedule_slot_(wbc_gait g, int* device, const double** cmd, const d
   *device = g->device; *cmd = g->d_table ? g->cmd : nullptr; *start = g->start; *slot = &g->schedule;
   return 0;
 }
+
+// internal: what wbc_gait_feedback.hip needs of a handle -- its device, the stride table on the device (NULL: no
+// wbc_gait_set_commands yet) with its count, the gait_id and stride_scale of wbc_gait_set_commands, the number of terrain profiles
+// (0: no terrain) and the slot that keeps that file's state
+int wbc_gait_feedback_slot_(wbc_gait g, int* device, int* count, int* terrain_count, const double** table, const uint8_t** gait_id,
+                            const double** scale, wbc::GaitFeedbackState*** slot) {
+  *device = g->device; *count = g->count; *terrain_count = g->terrain.count; *table = g->cmd ? g->d_table : nullptr;
+  *gait_id = g->gait_id; *scale = g->scale; *slot = &g->feedback;
+  return 0;
+}
+
+// internal: whether wbc_gait_set_feedback holds on the handle -- the rollouts then take wbc_gait_targets_measured as their source
+int wbc_gait_feedback_on_(wbc_gait g) { return wbc::gait_feedback_on(g->feedback) ? 1 : 0; }
 
 int wbc_gait_kernel_info(wbc_gait g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
   if (!g) return wbc::misuse("wbc_gait_kernel_info: null gait handle");

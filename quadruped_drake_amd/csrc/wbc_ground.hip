@@ -15,6 +15,7 @@
 #include "../../include/wbc.h"
 #include "../../include/wbc_ground.h"
 #include "../../include/wbc_gait.h"
+#include "wbc_gait_feedback.h"   // include_gait_feedback/: on the include path (build())
 #include "wbc_model.hpp"
 #include "wbc_tick.hpp"
 #include "wbc_ground.hpp"
@@ -23,6 +24,7 @@
 #include "wbc_plant_host.hpp"
 
 extern "C" int wbc_gait_device_(wbc_gait g);   // wbc_gait.hip (internal): the device a gait handle was created for
+extern "C" int wbc_gait_feedback_on_(wbc_gait g);   // wbc_gait.hip (internal): whether wbc_gait_set_feedback holds on the handle
 
 namespace {
 
@@ -402,8 +404,11 @@ int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stre
   const GroundArgs a = make_args(g, n, ld, sub, dt, q, v, time, tau, ground_mu, ground_mass_scale, ext_wrench, nullptr, force, contact,
                                  flags, counts);
   const bool follow = g->follow != WBC_FOLLOW_OFF && g->terrain.count > 0;   // otherwise: the launches of a rollout without it
-  // the tick's targets: the gait's while one is set, else the lookup in `traj` -- the launch a rollout without a gait issues
+  // the tick's targets: the gait's while one is set, else the lookup in `traj` -- the launch a rollout without a gait issues.  A
+  // gait with feedback set (wbc_gait_feedback.h) reads the rollout's own q and v: one more launch per tick.
+  const bool measured = g->gait && wbc_gait_feedback_on_(g->gait);
   auto source = [&](wbc_traj tr, void* s, int n_, int ld_, const double* t, double* tg, uint8_t* m) {
+    if (measured) return wbc_gait_targets_measured(g->gait, s, n_, ld_, t, q, v, tg, m, nullptr);
     return g->gait ? wbc_gait_targets(g->gait, s, n_, ld_, t, tg, m) : wbc_traj_lookup(tr, s, n_, ld_, t, tg, m);
   };
   return wbc::plant_rollout("wbc_ground_rollout", h, traj, g->device, hip_stream, steps, n, ld, q, v, time, targets, contact_mask, mu,

@@ -10,6 +10,8 @@ finished targets on that ground -- footholds off the risers, swings that clear t
 follow pass runs after them.
 `GaitPlanner.set_schedule` steers it (include_gait_schedule/wbc_gait_schedule.h): every robot walks its own sequence of commands,
 switched at its own times and joined by smooth turns -- up to a kerb and along it, a square, to a stop, into reverse.
+`GaitPlanner.set_feedback` closes the loop on the footholds (include_gait_feedback/wbc_gait_feedback.h): a pass after the gait's kernel
+shifts every swing's landing point by what the measured trunk velocity asks for, so that a pushed robot steps after its trunk.
 Torch tensors and torch's current stream, as in controller.py and plant.py.
 """
 import ctypes as C
@@ -147,6 +149,7 @@ class GaitPlanner:
         self._keep = None
         self._terrain = None
         self._schedule = None
+        self._feedback = None
         h = C.c_void_p()
         _lib.check(self._L.wbc_gait_create(C.byref(self.params), c_strides(self.strides), len(self.strides), self.device, C.byref(h)))
         self._h = h
@@ -197,6 +200,60 @@ class GaitPlanner:
     def schedule_kernel_info(self, terrain=False):
         """kernel_info() of the kernel that runs while a schedule is set, without or with a terrain."""
         return _lib.kernel_info(lambda h, *out: self._L.wbc_gait_schedule_kernel_info(h, int(bool(terrain)), *out), self._h)
+
+    def feedback_defaults(self):
+        """dict(k_v, k_p, d_max, u_hold) of wbc_gait_feedback_params_default for this planner's body height."""
+        p = _lib.WbcGaitFeedbackParams()
+        _lib.check(self._L.wbc_gait_feedback_params_default(C.byref(self.params), C.byref(p)))
+        return dict(k_v=p.k_v, k_p=p.k_p, d_max=p.d_max, u_hold=p.u_hold)
+
+    def set_feedback(self, n, **params):
+        """Let the footholds react to the measured trunk (include_gait_feedback/wbc_gait_feedback.h): allocates and zeroes the state
+        of n robots; called again, it resets it.  params: k_v [s], k_p, d_max [m], u_hold over feedback_defaults().  From then on
+        targets_measured() works, and a rollout that takes this planner (plant.closed_loop) feeds it its own q and v; targets() is
+        unchanged.  Not with a terrain.  Synchronises the device."""
+        d = self.feedback_defaults()
+        unknown = set(params) - set(d)
+        if unknown:
+            raise ValueError("set_feedback: unknown parameter %s; expected k_v, k_p, d_max, u_hold" % ", ".join(sorted(unknown)))
+        d.update({k: float(x) for k, x in params.items()})
+        p = _lib.WbcGaitFeedbackParams(**d)
+        _lib.check(self._L.wbc_gait_set_feedback(self._h, C.byref(p), int(n)))
+        self._feedback = (int(n), d)
+
+    def clear_feedback(self):
+        """The planner is a function of the time again; rollouts issue the launches they issue without feedback."""
+        _lib.check(self._L.wbc_gait_clear_feedback(self._h))
+        self._feedback = None
+
+    @property
+    def has_feedback(self):
+        return getattr(self, "_feedback", None) is not None
+
+    def feedback_kernel_info(self):
+        """kernel_info() of the feedback pass's kernel."""
+        return _lib.kernel_info(self._L.wbc_gait_feedback_kernel_info, self._h)
+
+    def targets_measured(self, time, q, v, out=None, offsets=None):
+        """targets(time, out), then the feedback pass on the measured q [19, N] and v [18, N]: the foot rows shifted, the state
+        advanced by one call.  offsets: an optional [8, N] float64 tensor that receives the (x, y) offset of each foot.  Needs
+        set_feedback.  Asynchronous on torch's current stream."""
+        import torch
+        if self._n is None:
+            raise ValueError("GaitPlanner.targets_measured: set_commands first")
+        n, d = self._n, self.device
+        pt = _lib.dev_ptr(time, 0, n, torch.float64, "time", d, "the planner")
+        pq = _lib.dev_ptr(q, 19, n, torch.float64, "q", d, "the planner")
+        pv = _lib.dev_ptr(v, 18, n, torch.float64, "v", d, "the planner")
+        if out is None:
+            out = (torch.empty((54, n), dtype=torch.float64, device="cuda:%d" % d), torch.empty((n,), dtype=torch.uint8, device="cuda:%d" % d))
+        tg, mk = out
+        ptg = _lib.dev_ptr(tg, 54, n, torch.float64, "targets", d, "the planner")
+        pmk = _lib.dev_ptr(mk, 0, n, torch.uint8, "contact_mask", d, "the planner")
+        pof = _lib.dev_ptr(offsets, 8, n, torch.float64, "offsets", d, "the planner", True)
+        s = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
+        _lib.check(self._L.wbc_gait_targets_measured(self._h, s, n, n, pt, pq, pv, ptg, pmk, pof))
+        return tg, mk
 
     def targets(self, time, out=None):
         """-> (targets [54, N] float64, contact_mask [N] uint8) at time [N] float64; out: such a pair to write into.  Asynchronous on
@@ -270,6 +327,7 @@ class GaitPlanner:
             self._keep = None
             self._terrain = None
             self._schedule = None
+            self._feedback = None
 
     def __del__(self):
         try:

@@ -30,7 +30,11 @@ smooth turn of length B (default 0.5) after each of up to seven switches (includ
 spreads the first command only.
 `--gait-terrain lift|fit` (with `--planner gait` and `--terrain`; default `off`; excludes `--follow`) gives the plant's terrain to the
 planner (include/wbc_gait_terrain.h): footholds on the surface and off the risers, swings that clear what lies between
-their footholds, a body that follows the feet (`fit`: also in pitch and roll).  That is what walks a kerb of 0.1 m."""
+their footholds, a body that follows the feet (`fit`: also in pitch and roll).  That is what walks a kerb of 0.1 m.
+`--gait-feedback [KV,KP,DMAX,UHOLD]` (with `--planner gait`, without `--gait-terrain`) lets the footholds react to the measured trunk
+(include_gait_feedback/wbc_gait_feedback.h): a velocity gain [s], a position gain, the largest offset [m] and the swing fraction up to
+which a landing point still moves; without a value, wbc_gait_feedback_params_default's.  `--push T0:T1:FX,FY` (with `--plant ground`)
+applies the world force FX,FY [N] to every trunk during [T0, T1) seconds, by splitting the rollout into calls at T0 and T1."""
 import argparse
 import json
 import sys
@@ -70,6 +74,9 @@ def parse(argv=None):
     ap.add_argument("--cmd-blend", type=float, default=0.5, help="--cmd-schedule: the length of the smooth turn after a switch [s]")
     ap.add_argument("--gait-terrain", default="off", choices=("off", "lift", "fit"),
                     help="--planner gait with --terrain only: the planner walks ON the terrain (lift: body height; fit: and its attitude)")
+    ap.add_argument("--gait-feedback", nargs="?", const="default", default=None,
+                    help="gait planner: footholds react to the measured trunk; optional KV,KP,DMAX,UHOLD (default: the capture-point gain)")
+    ap.add_argument("--push", default=None, help="--plant ground only: T0:T1:FX,FY -- a world force [N] on every trunk during [T0, T1) s")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
@@ -106,6 +113,32 @@ def parse(argv=None):
             a.cmd_schedule = items
     if a.cmd_schedule is not None and a.planner != "gait":
         ap.error("--cmd-schedule needs --planner gait")
+    if a.gait_feedback is not None:
+        if a.planner != "gait":
+            ap.error("--gait-feedback needs --planner gait")
+        if a.gait_terrain != "off":
+            ap.error("--gait-feedback excludes --gait-terrain: the feedback knows no terrain")
+        if a.gait_feedback == "default":
+            a.gait_feedback = {}
+        else:
+            try:
+                val = tuple(float(x) for x in a.gait_feedback.split(","))
+            except ValueError:
+                val = ()
+            if len(val) != 4 or not all(np.isfinite(val)) or min(val) < 0 or val[2] == 0 or val[3] > 1:
+                ap.error("--gait-feedback: expected KV,KP,DMAX,UHOLD, finite and >= 0, DMAX > 0, UHOLD <= 1")
+            a.gait_feedback = dict(zip(("k_v", "k_p", "d_max", "u_hold"), val))
+    if a.push is not None:
+        if a.plant != "ground":
+            ap.error("--push needs --plant ground")
+        try:
+            t0, t1, f = a.push.split(":")
+            val = (float(t0), float(t1)) + tuple(float(x) for x in f.split(","))
+        except ValueError:
+            val = ()
+        if len(val) != 4 or not all(np.isfinite(val)) or not 0 <= val[0] < val[1]:
+            ap.error("--push: expected T0:T1:FX,FY with 0 <= T0 < T1, all finite")
+        a.push = val
     if a.terrain is not None:
         if a.plant != "ground":
             ap.error("--terrain needs --plant ground")
@@ -180,17 +213,25 @@ def run(a):
                           start=torch.tensor(np.stack([q0[4], q0[5], np.zeros(a.n)]), device=dev))
         if a.cmd_schedule is not None:
             traj.set_schedule([t for t, _ in a.cmd_schedule], [c for _, c in a.cmd_schedule], blend=a.cmd_blend)
+        if a.gait_feedback is not None:
+            traj.set_feedback(a.n, **a.gait_feedback)
     steps = int(round(a.sim_time / a.dt))
+    push, edges = None, ()
+    if a.push is not None:              # the force is an argument of a rollout call: the calls are split at its two ends
+        edges = (int(round(a.push[0] / a.dt)), int(round(a.push[1] / a.dt)))
+        w = np.zeros((6, a.n)); w[3] = a.push[2]; w[4] = a.push[3]
+        push = torch.tensor(w, device=dev)
     ts, mets = [], []
     ctrl.stats(reset=True)
     ctrl.sync(); t0 = _time.perf_counter()
     done = 0
     while done < steps:
-        k = min(a.log_every, steps - done)
+        k = min([a.log_every, steps - done] + [e - done for e in edges if e > done])
+        pushing = push is not None and edges[0] <= done < edges[1]
         if plant is None:
             tau, met, st, tg, mk = ctrl.rollout(traj, k, a.dt, q, v, time)
         else:
-            met = plant_mod.closed_loop(ctrl, plant, traj, k, a.dt, q, v, time, counts=counts)[1]
+            met = plant_mod.closed_loop(ctrl, plant, traj, k, a.dt, q, v, time, counts=counts, **(dict(ext_wrench=push) if pushing else {}))[1]
         done += k
         ts.append(done * a.dt); mets.append(met.clone())
     ctrl.sync(); wall = _time.perf_counter() - t0
@@ -228,6 +269,10 @@ def main(argv=None):
                          plan_offset_mean=r["plan_offset"]["mean"], plan_offset_worst=r["plan_offset"]["worst"])
             if a.cmd_schedule is not None:
                 extra.update(cmd_schedule=[[t] + list(c) for t, c in a.cmd_schedule], cmd_blend=a.cmd_blend)
+            if a.gait_feedback is not None:
+                extra.update(gait_feedback=a.gait_feedback)
+        if a.push is not None:
+            extra.update(push=list(a.push))
     print(json.dumps({"control": a.control, "planner": a.planner, "scenario": a.scenario if a.planner == "basic" else a.gait if a.planner == "gait" else a.messages,
                       "n": a.n, "sim_time": a.sim_time, "dt": a.dt, "ticks": r["ticks"], "status_nonzero": r["status_nonzero"],
                       "ticks_per_second": r["ticks_per_second"], "active_set_iterations_mean": r["iters_mean"],

@@ -3,7 +3,7 @@
 (include/wbc_gait_terrain.h) for profiles/r14/gait_terrain.md.
 
     python tools/gait_bench.py kernel [--n 4096] [--bursts 30] [--burst 20]
-    python tools/gait_bench.py loop --source traj|gait|gait_terrain|gait_follow|gait_schedule [--n 4096] [--steps 300] [--repeats 5]
+    python tools/gait_bench.py loop --source traj|gait|gait_terrain|gait_follow|gait_schedule|gait_feedback [--n 4096] [--steps 300] [--repeats 5]
 
   kernel: device time per launch of wbc_gait_targets_kernel (a trot, per-instance commands, scales and starts, times spread over
     3 s) and of the target-lookup kernel beside it: HIP events around bursts of back-to-back launches after a warm-up, the median
@@ -11,14 +11,17 @@
     planner on sixteen kerbs and stairs, each instance with its own profile and scale, FIT.  A library with the command schedules
     (include_gait_schedule/wbc_gait_schedule.h) also gets wbc_gait_schedule_targets_kernel and wbc_gait_schedule_terrain_targets_kernel
     timed: the same planner, every instance with its own three switches inside the 3 s of sampled times, blend 0.5 -- and the plain
-    kernels again once the schedule is cleared.
+    kernels again once the schedule is cleared.  A library with the foot-placement feedback (include_gait_feedback/wbc_gait_feedback.h)
+    gets wbc_gait_targets_measured timed, which is the plain kernel and wbc_gait_feedback_kernel after it: two launches; the pass's
+    own time is that pair's less the plain kernel's.
   loop: time per 1 ms tick of wbc_ground_rollout at 16 substeps, MPTC, with the targets looked up in a recorded trot
     (tools/follow_bench.py's; `traj`: the launches the rollout issued before it could take a gait) or computed by the gait (`gait`:
     a trot at stride scale 0.5, commands over +-0.3 m/s and +-0.5 rad/s).  One figure per process; the caller runs them in turn.  A
     library from before the gait planner (WBC_HIP_LIB) is measured with `--source traj`, which calls nothing it lacks.
     `gait_terrain`: the plant on sixteen kerbs and stairs and the gait on the same terrain (one terrain kernel per tick);
     `gait_follow`: the same ground under the plain gait with the follow law in FIT after it (two kernels per tick), the path a
-    terrain gait replaces.  `gait_schedule`: `gait` steered by three switches per instance (one schedule kernel per tick).
+    terrain gait replaces.  `gait_schedule`: `gait` steered by three switches per instance (one schedule kernel per tick).  `gait_feedback`: `gait` with the default feedback set, fed with the
+    rollout's q and v (the plain kernel and the feedback kernel per tick); its state is reset before every repeat.
 Both print one JSON line."""
 import argparse
 import json
@@ -96,6 +99,17 @@ def kernel(a):
         res["gait_terrain_after_clear_schedule"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
         p.clear_terrain()
         res["gait_after_clear_schedule"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
+    if hasattr(p._L, "wbc_gait_targets_measured"):
+        q0, v0 = workloads.nominal_state("mini_cheetah", a.n)
+        q, v = torch.tensor(q0, device=dev), torch.tensor(v0, device=dev)
+        v[3] = 0.2; v[4] = 0.1                                    # a trunk off its plan: the offsets are not zero
+        off = torch.zeros((8, a.n), dtype=torch.float64, device=dev)
+        p.set_feedback(a.n)
+        res["feedback_kernel"] = p.feedback_kernel_info()
+        res["gait_measured_pair"] = _burst_us(lambda: p.targets_measured(tm, q, v, out=out), lambda: None, a.bursts, a.burst)
+        res["gait_measured_pair_with_offsets"] = _burst_us(lambda: p.targets_measured(tm, q, v, out=out, offsets=off), lambda: None, a.bursts, a.burst)
+        p.clear_feedback()
+        res["gait_after_clear_feedback"] = _burst_us(lambda: p.targets(tm, out=out), lambda: None, a.bursts, a.burst)
     st_t = workloads.standing_targets("mini_cheetah", 1)[:, 0]
     K = 4000
     traj = TrunkTrajectory(np.arange(K) * 1e-3, np.tile(st_t, (K, 1)), np.full(K, 15, np.uint8), wait_time=0.0, device=0,
@@ -141,6 +155,8 @@ def loop(a):
     us = []
     for _ in range(a.repeats + 1):               # every repeat from the same start: the same ticks; the first is the warm-up
         q, v, t = torch.tensor(q0, device=dev), torch.tensor(v0, device=dev), torch.tensor(t0, device=dev)
+        if a.source == "gait_feedback":
+            src.set_feedback(n)
         closed_loop(ctrl, plant, src, 20, dt, q, v, t)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -162,7 +178,7 @@ def main():
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--bursts", type=int, default=30)
     ap.add_argument("--burst", type=int, default=20)
-    ap.add_argument("--source", default="traj", choices=("traj", "gait", "gait_terrain", "gait_follow", "gait_schedule"))
+    ap.add_argument("--source", default="traj", choices=("traj", "gait", "gait_terrain", "gait_follow", "gait_schedule", "gait_feedback"))
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
