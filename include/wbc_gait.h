@@ -51,7 +51,11 @@
  *
  *   Malformed instances -- a gait_id >= count, a stride_scale that is not positive and finite, a non-finite command, start or time --
  *   get all 54 rows NaN and mask 0xF; the tick then answers status 2 as it does for any NaN target.  Other instances are not touched
- *   by them.
+ *   by them.  An instance whose clock does not resolve in double is malformed as well: T = s B_nphase is zero or not finite (at any
+ *   time); or, for tau >= 0, k T is not finite, or for some foot that has a run the run [a, b) of the phase in progress, a and b formed
+ *   as the law forms them (k T + s B, in double), does not have b - a positive and finite.  A foot that is in contact in every phase
+ *   has no run and decides nothing here.  (A stride scale of 1e-17, a time of 1e300 s: both ends of a run round to one double.)  So no
+ *   instance is answered half in NaN.
  *
  *   The limits.  Without a terrain set on the handle (wbc_gait_terrain.h) the swing knows no terrain: over a
  *   knot the follow law (wbc_ground.h) lifts a swing target by the height under it, and the target jumps at a riser; and footholds

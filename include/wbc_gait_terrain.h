@@ -50,7 +50,7 @@
  *     -P' / (1 + P^2) and -(P'' (1 + P^2) - 2 P P'^2) / (1 + P^2)^2 with P', P'' the same sums over the rates of g_f; for roll their
  *     negatives in Q.  A stance with sum xt^2 = 0 or sum yt^2 = 0 is refused with FIT.  The yaw rows are wbc_gait.h's.
  *
- *   Malformed instances.  In addition to wbc_gait.h's: a terrain_id >= count or a terrain_scale that is not finite gives 54 NaN rows
+ *   Malformed instances.  In addition to wbc_gait.h's (a clock that does not resolve in double among them): a terrain_id >= count or a terrain_scale that is not finite gives 54 NaN rows
  *   and mask 0xF; its neighbours are not touched.
  *
  *   The limits.  The profile varies along one direction only.  The cap apex_max may bite, and then the clearance above is not

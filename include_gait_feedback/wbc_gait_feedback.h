@@ -20,7 +20,7 @@
  *     |d_raw| = sqrt(d_raw_x^2 + d_raw_y^2),   d = d_raw min(1, d_max / |d_raw|),   d = 0 when |d_raw| = 0.
  *   Every operation of the pass is rounded once: nothing is contracted into a fused multiply-add, as in wbc_gait.h's clock.
  *   An instance is left exactly as it is -- rows, state and previous mask -- when one of those eight numbers, one of its 54 target
- *   rows (the gait's NaN answer to a malformed instance) or its time is not finite; `offsets` gets NaN for it.  Its neighbours are
+ *   rows (the gait's NaN answer to a malformed instance, wbc_gait.h's unresolved clock included) or its time is not finite; `offsets` gets NaN for it.  Its neighbours are
  *   not touched by it.
  *
  *   Per foot f.  The clock is wbc_gait.h's.  With e the six numbers of the packed stride for (foot, phase), a = k T + s e[0] and

@@ -36,7 +36,8 @@
  *   beta > 0 (beta = 0: the pose is continuous, the velocity jumps at Theta_j).
  *
  *   Malformed instances.  An invalid schedule (m > 7 included) gets 54 NaN rows and mask 0xF, like every other malformed instance;
- *   its neighbours keep their bits.
+ *   its neighbours keep their bits.  wbc_gait.h's list holds under a schedule as it stands, a clock that does not resolve in double
+ *   included.
  *
  *   Exact relation.  An instance with m = 0 gets the bits of the law without a schedule, and so does any instance while all three
  *   of its pose evaluations lie before Theta_1.

@@ -222,6 +222,16 @@ WBC_HD GaitClock gait_clock(const double* table, int count, const GaitIn& in) {
   WBC_GAIT_UNROLL
   for (int m = 0; m < 7; m++) j += (r >= c.s * c.stride[m]) ? 1 : 0;
   c.phase = j;
+  // a clock that does not resolve in double is malformed too (the header's rule): T, and from tau = 0 on k T and the run [a, b) of
+  // every foot that has one -- a and b as gait_foot forms them, the -inf of a foot that is always down exempt
+  bool lost = !(T > 0.0) | not_finite(T);
+  WBC_GAIT_UNROLL
+  for (int f = 0; f < 4; f++) {
+    const double* e = c.stride + 12 + 6 * (8 * f + j);
+    const double a = c.kT + c.s * e[0], b = c.kT + c.s * e[1], D = b - a;
+    lost |= !c.pre & (e[0] != -INFINITY) & (!(D > 0.0) | not_finite(D));
+  }
+  c.bad |= lost | (!c.pre & not_finite(c.kT));
   c.mask = (c.bad | c.pre) ? 0xFu : (((unsigned)c.stride[8] >> (4 * j)) & 0xFu);
   return c;
 }

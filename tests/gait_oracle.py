@@ -72,7 +72,8 @@ def pose(th, c, w, start, dtype=np.float64):
 
 
 def _rot(psi, x, y):
-    return np.stack([np.cos(psi) * x - np.sin(psi) * y, np.sin(psi) * x + np.cos(psi) * y])
+    c, s = np.cos(psi), np.sin(psi)
+    return np.stack([c * x - s * y, s * x + c * y])
 
 
 def clock(durations, tau, s, dtype=np.float64):
@@ -88,6 +89,27 @@ def clock(durations, tau, s, dtype=np.float64):
     for j in range(1, len(durations)):
         phase += r >= s * dtype(B[j])
     return k, kT, r, phase
+
+
+def unresolved(durations, masks, tau, s):
+    """[n] bool, the header's "clock that does not resolve in double" -- always evaluated in double, whatever precision the rows are
+    computed in: T = s B_n zero or not finite; or, for tau >= 0, k T not finite, or a foot that has a run whose run [a, b) of the phase
+    in progress (a = k T + s B_lo, b = k T + s B_hi) does not have b - a positive and finite."""
+    tau, s = np.asarray(tau, np.float64), np.asarray(s, np.float64)
+    B = boundaries(durations)
+    with np.errstate(all="ignore"):
+        T = s * B[-1]
+        lost = ~(T > 0) | ~np.isfinite(T)
+        k, kT, _, phase = clock(durations, np.where(tau < 0, 0.0, tau), s)
+        walking = ~(tau < 0)
+        lost |= walking & ~np.isfinite(kT)
+        for j in range(len(durations)):
+            for f in range(4):
+                _, lo, hi, _, _ = runs(masks, f, j)
+                if lo is not None:
+                    D = (kT + s * boundary(B, hi)) - (kT + s * boundary(B, lo))
+                    lost |= walking & (phase == j) & (~(D > 0) | ~np.isfinite(D))
+    return lost
 
 
 def boundary_distance(durations, time, wait_time, s):
@@ -118,6 +140,7 @@ def targets(params, strides, time, cmd, gait_id=None, stride_scale=None, start=N
     H, hs, ramp, wait = (params[k] for k in ("height", "swing_height", "ramp_time", "wait_time"))
     for g, (durations, masks) in enumerate(strides):
         sel = np.nonzero(~bad & (gid == g))[0]
+        sel = sel[~unresolved(durations, masks, time[sel] - np.float64(wait), sc[sel])]      # malformed too: NaN rows, mask 0xF
         if sel.size == 0:
             continue
         t = time[sel].astype(dtype)
@@ -150,6 +173,14 @@ def targets(params, strides, time, cmd, gait_id=None, stride_scale=None, start=N
             pm, psim = pose(thm, c, w, st, dtype)
             return pm + _rot(psim, dtype(stance[f, 0]), dtype(stance[f, 1]))
 
+        known = {}
+
+        def foothold_of(f, lo, hi):
+            """foothold() of the stance run between boundaries lo and hi; a stride's phases share their runs, so each is computed once"""
+            if (f, lo, hi) not in known:
+                known[(f, lo, hi)] = foothold(f, None if lo is None else at(lo), None if lo is None else at(hi))
+            return known[(f, lo, hi)]
+
         m = np.zeros(sel.size, np.uint8)
         for j in range(len(durations)):
             inj = ~pre & (phase == j)
@@ -159,10 +190,10 @@ def targets(params, strides, time, cmd, gait_id=None, stride_scale=None, start=N
                 rows = slice(18 + 9 * f, 27 + 9 * f)
                 val = np.zeros((9, sel.size), dtype)
                 if contact:
-                    val[0:2] = foothold(f, None if lo is None else at(lo), None if lo is None else at(hi))
+                    val[0:2] = foothold_of(f, lo, hi)
                 else:
                     a, b = at(lo), at(hi)
-                    A, Bf = foothold(f, at(plo), a), foothold(f, b, at(nhi))
+                    A, Bf = foothold_of(f, plo, lo), foothold_of(f, hi, nhi)
                     D = b - a
                     u = (tau - a) / D
                     val[0:2] = A + (Bf - A) * (10 * u**3 - 15 * u**4 + 6 * u**5)
@@ -175,7 +206,7 @@ def targets(params, strides, time, cmd, gait_id=None, stride_scale=None, start=N
         m[pre] = 0xF
         for f in range(4):                       # tau < 0: the start stance
             val = np.zeros((9, sel.size), dtype)
-            val[0:2] = foothold(f, None, None)
+            val[0:2] = foothold_of(f, None, None)
             o[18 + 9 * f:27 + 9 * f, :] = np.where(pre, val, o[18 + 9 * f:27 + 9 * f, :])
         out[:, sel] = o
         mask[sel] = m

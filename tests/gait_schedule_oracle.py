@@ -66,6 +66,8 @@ class Schedule:
         x, y = p[0], p[1]
         for j in range(MAX_SWITCHES):
             used = j < self.m
+            if not used.any():                                                           # no instance has a switch j: nothing below selects
+                break
             Th = np.where(used, self.when[j], dt(0))
             cj = [np.where(used, self.cmds[3 * j + d], dt(0)) for d in range(3)]
             pE, psiE = _arc(Th - org, np.stack([cx, cy]), w, np.stack([sx, sy, sp]), dt)
@@ -142,6 +144,7 @@ def targets(params, strides, time, cmd, nswitch, when, cmds, blend, gait_id=None
     for g in range(len(strides)):
         for pi in range(1 if profiles is None else len(profiles)):
             sel = np.nonzero(~bad & (gid == g) & ((tid == pi) | (profiles is None)))[0]
+            sel = sel[~go.unresolved(strides[g][0], strides[g][1], time[sel] - np.float64(wait), sc[sel])]      # wbc_gait.h's unresolved clock
             if sel.size == 0:
                 continue
             S = Schedule(cmd[:, sel], st0[:, sel], np.asarray(nswitch)[sel], when[:, sel], cmds[:, sel], blend, dtype)

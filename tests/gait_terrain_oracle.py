@@ -115,6 +115,7 @@ def targets(params, strides, tp, profiles, time, cmd, gait_id=None, stride_scale
     for g, (durations, masks) in enumerate(strides):
         for pi, prof in enumerate(profiles):
             sel = np.nonzero(~bad & (gid == g) & (tid == pi))[0]
+            sel = sel[~go.unresolved(durations, masks, time[sel] - np.float64(wait), sc[sel])]      # wbc_gait.h's unresolved clock
             if sel.size == 0:
                 continue
             m_ = sel.size
@@ -151,6 +152,14 @@ def targets(params, strides, tp, profiles, time, cmd, gait_id=None, stride_scale
                 F = pm + go._rot(psim, stance[f, 0], stance[f, 1])
                 return place(prof, scale, tp, F, fixed, dtype) + (fixed,)
 
+            known = {}
+
+            def foothold_of(f, lo, hi):
+                """foothold() of the stance run between boundaries lo and hi; a stride's phases share their runs: each is computed once"""
+                if (f, lo, hi) not in known:
+                    known[(f, lo, hi)] = foothold(f, None if lo is None else at(lo), None if lo is None else at(hi))
+                return known[(f, lo, hi)]
+
             G = np.zeros((4, 3, m_), dtype)                  # the ground height under each foot and its two rates
             near = np.full(m_, np.inf, dtype)
             fixed_now = np.zeros((4, m_), bool)
@@ -164,14 +173,14 @@ def targets(params, strides, tp, profiles, time, cmd, gait_id=None, stride_scale
                     val = np.zeros((9, m_), dtype)
                     gf = np.zeros((3, m_), dtype)
                     if contact:
-                        F, sF, zF, nr, fx = foothold(f, None if lo is None else at(lo), None if lo is None else at(hi))
+                        F, sF, zF, nr, fx = foothold_of(f, lo, hi)
                         val[0:2] = F; val[2] = zF
                         gf[0] = zF
                         sa, sb, za, zb, a_ = sF, sF, zF, zF, zero + dtype(hs)
                     else:
                         a, b = at(lo), at(hi)
-                        A, sa, za, n1, _ = foothold(f, at(plo), a)
-                        Bf, sb, zb, n2, fx = foothold(f, b, at(nhi))
+                        A, sa, za, n1, _ = foothold_of(f, plo, lo)
+                        Bf, sb, zb, n2, fx = foothold_of(f, hi, nhi)
                         nr = np.minimum(n1, n2)
                         D = b - a
                         u = (tau - a) / D
