@@ -248,8 +248,12 @@ int wbc_trunk_state_to_targets(const wbc_trunk_state* s, double* targets54, uint
 
 /* A stored trunk trajectory on the device and the per-tick lookup of planners/towr.py:92-106:
  * t < wait_time -> the standing targets (planners/simple.py:39-85), otherwise the sample whose
- * timestamp is nearest to t - wait_time (first index on ties: numpy argmin).  `timestamps` must be
- * non-decreasing; `targets` is [K][54] (one row per sample), `masks` [K]. */
+ * timestamp is nearest to t - wait_time: the index np.abs(timestamps - (t - wait_time)).argmin() returns, for every double t.
+ * In numpy's terms: with tq = t - wait_time and d[j] = |timestamps[j] - tq|, both ROUNDED to double, the first j whose d[j] is a
+ * NaN, else the first j of the smallest d[j] -- so equal timestamps, real ties and distances that only round to the same double
+ * all answer their first index (t = 1e17 or +inf against a finite table: every d is equal, sample 0), and a NaN t answers
+ * sample 0 (it is not < wait_time).  `timestamps` must be non-decreasing and hold no NaN (+-inf are accepted); `targets` is
+ * [K][54] (one row per sample), `masks` [K]. */
 int wbc_traj_create(int device, int K, const double* timestamps, const double* targets, const uint8_t* masks,
                     const double* standing_targets54, uint8_t standing_mask, double wait_time, wbc_traj* out);
 int wbc_traj_destroy(wbc_traj t);

@@ -1,7 +1,8 @@
 /*
  * wbc_extras.h -- exports of libwbc_hip.so that are NOT part of the controller interface of include/wbc.h:
  * callers and data formats either side of the hot path that earlier rounds widened into (the robot-side wire format of the
- * reference's use_lcm loop, its joint-space PD law).  Kept working and tested, frozen since round 3; a maintainer who binds the
+ * reference's use_lcm loop, its joint-space PD law).  Kept working and tested, frozen since round 3 but for the edges of their laws
+ * (round 18: NaN through the PD clip, the rule past FLT_MAX; tests/test_caller_edges_gpu.py); a maintainer who binds the
  * whole-body-QP path needs include/wbc.h only.
  */
 #ifndef WBC_EXTRAS_H
@@ -36,7 +37,10 @@ int wbc_robot_states_unpack(int device, void* hip_stream, int n, int ld, const u
                             uint8_t* ok);
 /* device, batched: tau[12][ld] in ACTUATOR order (what wbc_step wrote) -> n "robot_control_input" messages.
  * q_perm / act_perm: host int[12], the handle's model permutations (NULL = identity):
- * message.tau[q_perm[act_perm[k]]] = (float) tau[k].  Asynchronous on `hip_stream`. */
+ * message.tau[q_perm[act_perm[k]]] = (float) tau[k]: round to nearest even, float32 denormals kept, a NaN stays a NaN (payload not
+ * specified) -- the bytes of the reference's struct.pack('>f').  One rule of its own: a double that rounds past FLT_MAX (|x| >=
+ * 0x1.ffffffp127, the halfway point to 2^128, included) makes struct.pack raise OverflowError; the device cannot raise and writes
+ * +-inf, which the receiver's decoder reads as +-inf.  Asynchronous on `hip_stream`. */
 int wbc_robot_controls_pack(int device, void* hip_stream, int n, int ld, const double* tau, const int* q_perm,
                             const int* act_perm, uint8_t* msgs);
 
@@ -44,7 +48,9 @@ int wbc_robot_controls_pack(int device, void* hip_stream, int n, int ld, const d
  * The reference's joint-space PD law (control method "B": BasicController.ControlLaw, controllers/basic_controller.py:322-352),
  * batched and stateless: tau_v = -Kp N+(q)(q - q_nom) - Kd v, u = clip(S tau_v, -u_max, u_max).  S selects the twelve joint rows,
  * where N+ is the identity, so u[k] = clip(-(kp (q_j - q_nom_j)) - kd v_j) with j = the plant index of the joint actuator k drives
- * (j = q_perm[act_perm[k]]); evaluated without fused multiply-add, i.e. bit for bit what the reference's numpy computes.
+ * (j = q_perm[act_perm[k]]); evaluated without fused multiply-add and clipped by comparisons, i.e. bit for bit what the reference's
+ * numpy computes: a NaN joint angle or rate gives a NaN torque on that actuator (np.clip keeps a NaN; never a saturated torque), an
+ * infinite u clips, and at u_max = 0 the zeros carry np.clip's signs (u = +-0 kept, u > 0 -> +0.0, u < 0 -> -0.0).
  * q[19][ld], v[18][ld], tau[12][ld] (actuator order) are device pointers; q_nom19 is a HOST array in the plant's own joint order
  * (NULL = the reference's literal: base at (0, 0, 0.3), every leg (0, -0.8, 1.6)); the reference's gains are kp 30, kd 1.5, u_max 150.
  * q_perm / act_perm: host int[12], NULL = identity.  Asynchronous on `hip_stream`. */

@@ -92,7 +92,7 @@ __global__ void robot_controls_pack_kernel(int n, int ld, const double* __restri
   uint32_t out = 0u;
   if (c == 0) out = (uint32_t)(kRsFingerprint >> 32);
   else if (c == 1) out = (uint32_t)kRsFingerprint;
-  else if (c >= 39) out = __float_as_uint((float)tau[(size_t)src.k[c - 39] * ld + i]);   // round to nearest even, like struct.pack('>f')
+  else if (c >= 39) out = __float_as_uint((float)tau[(size_t)src.k[c - 39] * ld + i]);   // round to nearest even, like struct.pack('>f'); past FLT_MAX: +-inf (wbc_extras.h)
   w[(size_t)i * kRsWords + c] = bswap32(out);
 }
 
@@ -108,7 +108,9 @@ __global__ void pd_step_kernel(int n, int ld, const double* __restrict__ q, cons
   // -Kp@q_err - Kd@qd_err, then np.clip
   const double p1 = kp * qe, p2 = kd * v[(size_t)(6 + j) * ld + i];
   double u = -p1 - p2;
-  u = fmin(fmax(u, -u_max), u_max);
+  // np.clip by comparisons: a NaN passes (fmin / fmax would answer the bound: -u_max for a NaN state), and at u_max = 0 a u of
+  // either zero keeps its sign while a clipped one takes the bound's (-0.0 below, +0.0 above)
+  u = u < -u_max ? -u_max : (u > u_max ? u_max : u);
   tau[(size_t)k * ld + i] = u;
 }
 }  // namespace
@@ -235,8 +237,8 @@ int wbc_traj_create(int device, int K, const double* timestamps, const double* t
                     const double* standing_targets54, uint8_t standing_mask, double wait_time, wbc_traj* out) {
   if (!out || K < 0 || (K > 0 && (!timestamps || !targets || !masks)) || !standing_targets54)
     return misuse("wbc_traj_create: bad argument");
-  for (int i = 1; i < K; i++)
-    if (!(timestamps[i] >= timestamps[i - 1])) return misuse("wbc_traj_create: timestamps must be non-decreasing");
+  for (int i = 0; i < K; i++)   // (a NaN fails every comparison, its own included: refused at any K)
+    if (!(timestamps[i] >= timestamps[i > 0 ? i - 1 : 0])) return misuse("wbc_traj_create: timestamps must be non-decreasing");
   WBC_ON_DEVICE(device, fail);
   wbc_traj t = new wbc_traj_s();
   memset(t, 0, sizeof *t);

@@ -2,7 +2,8 @@
 (controllers/basic_controller.py:322-352) -- batched on the device: u = clip(S (-Kp N+(q)(q - q_nom) - Kd v), +-150).
 S selects the joint rows, where N+ is the identity, so the law is twelve multiply-subtracts per robot; it is here for the
 completeness of the controller family (simulate.py:13-17), not for its cost.  Bit-exact against the reference's executed
-code (tests/test_pd.py)."""
+code (tests/test_pd.py) and against np.clip at its edges -- a NaN angle or rate is a NaN torque, never a saturated one
+(tests/test_caller_edges_gpu.py)."""
 import ctypes as C
 
 import numpy as np

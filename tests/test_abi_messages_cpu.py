@@ -247,3 +247,9 @@ def test_wire_format_and_pd_argument_checks(L):
     mk = (C.c_uint8 * 3)()
     _says(L, L.wbc_traj_create(0, 3, ts, tg, mk, C.cast(tg, _lib.c_double_p), 15, 0.0, C.byref(h)),
           "wbc_traj_create: timestamps must be non-decreasing")
+    # a NaN timestamp is in no order: refused wherever it stands, in a table of one sample too (no neighbour to compare it with)
+    for K, where in ((1, 0), (2, 0), (2, 1), (3, 1)):
+        ts = (C.c_double * 3)(0.0, 1.0, 2.0)
+        ts[where] = float("nan")
+        _says(L, L.wbc_traj_create(0, K, ts, tg, mk, C.cast(tg, _lib.c_double_p), 15, 0.0, C.byref(h)),
+              "wbc_traj_create: timestamps must be non-decreasing")
