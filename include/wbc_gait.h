@@ -63,9 +63,9 @@
  *   them: that header has the law and its own limits.  The law is a function of the time and the command
  *   arrays alone: a caller may rewrite cmd, gait_id, stride_scale or start between calls, and the body pose and the footholds then
  *   jump.  A command that changes along the way, with a blended transition and inside a rollout too, is a schedule
- *   (include_gait_schedule/wbc_gait_schedule.h: up to seven switches per instance, joined by smooth turns); the stride and its scale
+ *   (include/wbc_gait_schedule.h: up to seven switches per instance, joined by smooth turns); the stride and its scale
  *   still hold for the whole run.  wbc_gait_targets takes nothing from the measured state; footholds that react to the measured
- *   trunk are a pass after it (include_gait_feedback/wbc_gait_feedback.h: wbc_gait_targets_measured, on the plane only).  The
+ *   trunk are a pass after it (include/wbc_gait_feedback.h: wbc_gait_targets_measured, on the plane only).  The
  *   persistent wbc_rollout (wbc.h) takes no gait: its lookup is part of the tick kernels.
  *
  * Rollouts.  While a gait is set on a plant handle (wbc_ground_set_gait, wbc_plant_set_gait), wbc_ground_rollout / wbc_plant_rollout

@@ -6,7 +6,7 @@
  * The law (this project's definition).  The pass reads the 54 target rows and the contact mask that wbc_gait_targets just wrote, the
  * time, and the measured q and v (layout: wbc.h).  It keeps a small state per instance, in a buffer the gait handle owns, and it
  * adds an (x, y) offset to the foot rows.  It does not care which of the gait's kernels wrote the rows: a command schedule
- * (include_gait_schedule/wbc_gait_schedule.h) composes with no further code.
+ * (include/wbc_gait_schedule.h) composes with no further code.
  *
  *   Parameters.  k_v [s]: velocity gain;  k_p: position gain;  d_max [m] > 0: the largest offset;  u_hold in [0, 1]: the swing
  *   fraction up to which a swing's landing offset still follows the measurement.  All four finite and non-negative.

@@ -44,7 +44,7 @@
  *
  *   The limits.  The stride and the stride scale do not change along the schedule; the schedule itself is a plan: it takes nothing
  *   from the measured state.  What reacts to the measured trunk is a pass after it that shifts the footholds
- *   (include_gait_feedback/wbc_gait_feedback.h), with or without a schedule.  The persistent wbc_rollout (wbc.h) takes no gait.
+ *   (include/wbc_gait_feedback.h), with or without a schedule.  The persistent wbc_rollout (wbc.h) takes no gait.
  *
  * Rollouts take the gait handle as their target source (wbc_gait.h), so a schedule set on it steers wbc_ground_rollout and
  * wbc_plant_rollout with no further call.

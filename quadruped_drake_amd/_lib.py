@@ -153,18 +153,11 @@ PROTOTYPES = {
     "wbc_gait_terrain_check": (_I, [_GAITTP, _P, _I]),
     "wbc_gait_set_terrain": (_I, [_P, _GAITTP, _P, _I, _P, _P]),
     "wbc_gait_terrain_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
-}
-SYMBOLS = list(PROTOTYPES)
-# include_gait_schedule/wbc_gait_schedule.h: the gait planner's command schedules, a header in its own directory.  lib() binds these
-# when the library has them (tests/test_gait_schedule_cpu.py lays the rows beside that header's prototypes).
-PROTOTYPES_SCHEDULE = {
+    # wbc_gait_schedule.h: the gait planner's command schedules
     "wbc_gait_set_schedule": (_I, [_P, _P, _I, _I, _D, _P, _P, _P]),
     "wbc_gait_clear_schedule": (_I, [_P]),
     "wbc_gait_schedule_kernel_info": (_I, [_P, _I, _IP, _IP, _IP, _IP]),
-}
-# include_gait_feedback/wbc_gait_feedback.h: the gait planner's foot-placement feedback, likewise a header in its own directory, bound
-# when the library has the names (tests/test_gait_feedback_cpu.py lays the rows beside that header's prototypes)
-PROTOTYPES_FEEDBACK = {
+    # wbc_gait_feedback.h: the gait planner's foot-placement feedback
     "wbc_gait_feedback_check": (_I, [_GAITFP]),
     "wbc_gait_feedback_params_default": (_I, [_GAITP, _GAITFP]),
     "wbc_gait_set_feedback": (_I, [_P, _GAITFP, _I]),
@@ -172,11 +165,15 @@ PROTOTYPES_FEEDBACK = {
     "wbc_gait_targets_measured": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "wbc_gait_feedback_kernel_info": (_I, [_P, _IP, _IP, _IP, _IP]),
 }
+SYMBOLS = list(PROTOTYPES)
 # the names newer than the oldest kernel build still timed against (A/B timing: WBC_HIP_LIB; tools/qt.py --lib): the statistics
-# exchange, the follow law, the gait planner and its terrain
+# exchange, the follow law, the gait planner, its terrain, its command schedules and its foot-placement feedback
 _NEWER = ("wbc_stats_pack", "wbc_stats_reduce", "wbc_ground_follow_targets", "wbc_ground_set_follow", "wbc_ground_follow_kernel_info",
           "wbc_gait_check", "wbc_gait_create", "wbc_gait_destroy", "wbc_gait_set_commands", "wbc_gait_targets", "wbc_gait_kernel_info",
-          "wbc_ground_set_gait", "wbc_plant_set_gait", "wbc_gait_terrain_check", "wbc_gait_set_terrain", "wbc_gait_terrain_kernel_info")
+          "wbc_ground_set_gait", "wbc_plant_set_gait", "wbc_gait_terrain_check", "wbc_gait_set_terrain", "wbc_gait_terrain_kernel_info",
+          "wbc_gait_set_schedule", "wbc_gait_clear_schedule", "wbc_gait_schedule_kernel_info", "wbc_gait_feedback_check",
+          "wbc_gait_feedback_params_default", "wbc_gait_set_feedback", "wbc_gait_clear_feedback", "wbc_gait_targets_measured",
+          "wbc_gait_feedback_kernel_info")
 # what a library may lack: any library the terrain, a library under A/B timing the newer names too
 _MAY_LACK = ("wbc_terrain_check", "wbc_ground_set_terrain", "wbc_ground_terrain_kernel_info") + (_NEWER if "WBC_HIP_LIB" in os.environ else ())
 
@@ -205,10 +202,6 @@ def lib():
         l = C.CDLL(LIB_PATH)
         for name, (restype, argtypes) in PROTOTYPES.items():
             if not (name in _MAY_LACK and not hasattr(l, name)):
-                fn = getattr(l, name)
-                fn.restype, fn.argtypes = restype, argtypes
-        for name, (restype, argtypes) in list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_FEEDBACK.items()):
-            if hasattr(l, name):
                 fn = getattr(l, name)
                 fn.restype, fn.argtypes = restype, argtypes
         _lib = l

@@ -11,12 +11,10 @@
 // raises its swing over the knots between them, and the ground height under each foot and its two rates go round the quad by
 // wbc_quad.hpp's broadcasts for the body rows.  A handle with no terrain launches wbc_gait_targets_kernel, whose code is untouched.
 //
-// Command schedules (include_gait_schedule/wbc_gait_schedule.h) live in wbc_gait_schedule.hip, kernels and entry points: a translation
-// unit of their own, so that this one's device code stays what it was.  The handle here keeps that file's state behind one pointer
-// and hands a launch over to it while a schedule is set (wbc_gait_schedule_dev.hpp).
-//
-// The foot-placement feedback (include_gait_feedback/wbc_gait_feedback.h) lives in wbc_gait_feedback.hip in the same way: its state
-// hangs off the handle by one pointer, and wbc_gait_targets knows nothing of it.
+// Command schedules (include/wbc_gait_schedule.h) live in wbc_gait_schedule.hip and the foot-placement feedback
+// (include/wbc_gait_feedback.h) in wbc_gait_feedback.hip, kernels and entry points: translation units of their own, so that this
+// one's device code stays what it was.  The three share the handle (wbc_gait_handle.hpp); wbc_gait_targets hands a launch over to the
+// schedules' file while a schedule is set and knows nothing of the feedback.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -26,33 +24,12 @@
 #include "../../include/wbc_gait.h"
 #include "../../include/wbc_gait_terrain.h"
 #include "wbc_gait.hpp"
-#include "wbc_gait_schedule_dev.hpp"
-#include "wbc_gait_feedback.hpp"
+#include "wbc_gait_handle.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
 
-namespace {
-
-struct GaitArgs {
-  int n, ld, count;
-  const double* table;   // GAIT_HEAD + count * GAIT_STRIDE doubles
-  const double* time;
-  const double* cmd;
-  const uint8_t* gait_id;
-  const double* scale;
-  const double* start;
-  double* targets;
-  uint8_t* mask;
-};
-
-struct GaitTerrainArgs {
-  int count;             // profiles in the table; 0: no terrain
-  const double* table;   // GAIT_TERRAIN_HEAD + count * TERRAIN_STRIDE doubles
-  const uint8_t* id;
-  const double* scale;
-};
-
-}  // namespace
+using wbc::GaitArgs;
+using wbc::GaitTerrainArgs;
 
 // stable kernel name (rocprofv3 --kernel-trace)
 __global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_targets_kernel(GaitArgs a) {
@@ -144,20 +121,6 @@ __global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_terrain_targets_kern
   }
 }
 
-struct wbc_gait_s {
-  int device, count;
-  double table[wbc::GAIT_TABLE_DOUBLES];
-  double* d_table;       // allocated and filled by the first wbc_gait_set_commands
-  const double* cmd;     // nullptr: no wbc_gait_set_commands yet
-  const uint8_t* gait_id;
-  const double* scale;
-  const double* start;
-  double* d_terrain;       // the packed terrain table, GAIT_TERRAIN_DOUBLES doubles, allocated by the first wbc_gait_set_terrain
-  GaitTerrainArgs terrain; // count == 0: no terrain, the plain kernel
-  wbc::GaitScheduleState* schedule;   // wbc_gait_schedule.hip's; nullptr until the first wbc_gait_set_schedule
-  wbc::GaitFeedbackState* feedback;   // wbc_gait_feedback.hip's; nullptr unless wbc_gait_set_feedback holds
-};
-
 extern "C" {
 
 int wbc_gait_check(const wbc_gait_params* params, const wbc_gait_stride* strides, int count) {
@@ -171,29 +134,23 @@ int wbc_gait_create(const wbc_gait_params* params, const wbc_gait_stride* stride
   const char* what = wbc::gait_error(params, strides, count);
   if (what) return wbc::misuse("wbc_gait_create", what);
   if (device < 0) return wbc::misuse("wbc_gait_create: device must be >= 0");
-  wbc_gait g = new wbc_gait_s();
+  wbc_gait g = new wbc_gait_s();   // no commands, no terrain, no schedule, no feedback: all null and 0
   g->device = device;
   g->count = count;
   wbc::gait_pack(params, strides, count, g->table);
-  g->d_table = nullptr;
-  g->cmd = nullptr; g->gait_id = nullptr; g->scale = nullptr; g->start = nullptr;
-  g->d_terrain = nullptr;
-  g->terrain = GaitTerrainArgs{};
-  g->schedule = nullptr;
-  g->feedback = nullptr;
   *out = g;
   return 0;
 }
 
 int wbc_gait_destroy(wbc_gait g) {
   if (!g) return 0;
-  if (g->d_table || g->d_terrain || g->schedule || g->feedback) {
+  if (g->d_table || g->d_terrain || g->d_knots || g->d_feedback) {
     wbc::DeviceGuard device_guard_(g->device);
     (void)hipDeviceSynchronize();   // a launch still reading the tables
     if (g->d_table) (void)hipFree(g->d_table);
     if (g->d_terrain) (void)hipFree(g->d_terrain);
-    wbc::gait_schedule_free(g->schedule);
-    wbc::gait_feedback_free(g->feedback);
+    if (g->d_knots) (void)hipFree(g->d_knots);
+    if (g->d_feedback) (void)hipFree(g->d_feedback);
   }
   delete g;
   return 0;
@@ -222,20 +179,14 @@ int wbc_gait_targets(wbc_gait g, void* hip_stream, int n, int ld, const double* 
   const int rc = wbc::plant_check_batch("wbc_gait_targets", g, "gait", n, ld, time && targets && contact_mask, "time, targets and contact_mask");
   if (rc) return rc;
   if (!g->cmd || !g->d_table) return wbc::misuse("wbc_gait_targets: wbc_gait_set_commands has not been called on this handle");
-  if (wbc::gait_schedule_on(g->schedule) && n > g->schedule->args.n)
+  if (wbc::gait_schedule_on(*g) && n > g->schedule.n)
     return wbc::misuse("wbc_gait_targets: n is larger than the n of the handle's wbc_gait_set_schedule");
   if (n == 0) return 0;
   WBC_ON_DEVICE(g->device, wbc::fail);
-  if (wbc::gait_schedule_on(g->schedule)) {
-    wbc::GaitLaunch L;
-    L.n = n; L.ld = ld; L.count = g->count; L.table = g->d_table; L.time = time; L.cmd = g->cmd; L.gait_id = g->gait_id;
-    L.scale = g->scale; L.start = g->start; L.targets = targets; L.mask = contact_mask;
-    L.tcount = g->terrain.count; L.ttable = g->terrain.table; L.tid = g->terrain.id; L.tscale = g->terrain.scale;
-    return wbc::gait_schedule_launch(g->schedule, hip_stream, L);
-  }
   GaitArgs a;
   a.n = n; a.ld = ld; a.count = g->count; a.table = g->d_table; a.time = time; a.cmd = g->cmd; a.gait_id = g->gait_id;
   a.scale = g->scale; a.start = g->start; a.targets = targets; a.mask = contact_mask;
+  if (wbc::gait_schedule_on(*g)) return wbc::gait_schedule_launch(*g, hip_stream, a);
   if (g->terrain.count > 0)
     hipLaunchKernelGGL(wbc_gait_terrain_targets_kernel, wbc::plant_grid(n), dim3(wbc::QUAD_BLOCK), 0, (hipStream_t)hip_stream, a, g->terrain);
   else
@@ -243,29 +194,6 @@ int wbc_gait_targets(wbc_gait g, void* hip_stream, int n, int ld, const double* 
   HIP_TRY(hipGetLastError());
   return 0;
 }
-
-// internal (not in include/wbc_gait.h): the handle's device, for the plants' wbc_*_set_gait
-int wbc_gait_device_(wbc_gait g) { return g->device; }
-
-// internal: what wbc_gait_schedule.hip needs of a handle -- its device, the cmd and start of wbc_gait_set_commands (cmd NULL: none
-// yet) and the slot that keeps that file's state
-int wbc_gait_schedule_slot_(wbc_gait g, int* device, const double** cmd, const double** start, wbc::GaitScheduleState*** slot) {
-  *device = g->device; *cmd = g->d_table ? g->cmd : nullptr; *start = g->start; *slot = &g->schedule;
-  return 0;
-}
-
-// internal: what wbc_gait_feedback.hip needs of a handle -- its device, the stride table on the device (NULL: no
-// wbc_gait_set_commands yet) with its count, the gait_id and stride_scale of wbc_gait_set_commands, the number of terrain profiles
-// (0: no terrain) and the slot that keeps that file's state
-int wbc_gait_feedback_slot_(wbc_gait g, int* device, int* count, int* terrain_count, const double** table, const uint8_t** gait_id,
-                            const double** scale, wbc::GaitFeedbackState*** slot) {
-  *device = g->device; *count = g->count; *terrain_count = g->terrain.count; *table = g->cmd ? g->d_table : nullptr;
-  *gait_id = g->gait_id; *scale = g->scale; *slot = &g->feedback;
-  return 0;
-}
-
-// internal: whether wbc_gait_set_feedback holds on the handle -- the rollouts then take wbc_gait_targets_measured as their source
-int wbc_gait_feedback_on_(wbc_gait g) { return wbc::gait_feedback_on(g->feedback) ? 1 : 0; }
 
 int wbc_gait_kernel_info(wbc_gait g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
   if (!g) return wbc::misuse("wbc_gait_kernel_info: null gait handle");

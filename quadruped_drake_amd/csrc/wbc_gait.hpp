@@ -297,7 +297,7 @@ WBC_HD double gait_apex(const double* ter, const GaitGround& G, double swing_hei
   return fmin(ter[2], swing_height + m);
 }
 
-// ---------------------------------------------------------------- command schedules (include_gait_schedule/wbc_gait_schedule.h)
+// ---------------------------------------------------------------- command schedules (include/wbc_gait_schedule.h)
 // wbc_gait_set_schedule resolves every instance's switches once (gait_schedule_resolve, one thread per instance) into GAIT_KNOT_ROWS
 // rows per switch of a buffer [7 * GAIT_KNOT_ROWS][ld]; the SCHEDULE instantiations of gait_foot and gait_body then find a path
 // parameter's segment by seven compares and read that switch's rows only (gait_schedule_pose).  Rows of switch j (0-based):

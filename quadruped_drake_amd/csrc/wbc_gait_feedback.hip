@@ -1,4 +1,4 @@
-// wbc_gait_feedback.hip -- the gait planner's foot-placement feedback (include_gait_feedback/wbc_gait_feedback.h): kernel and C ABI.
+// wbc_gait_feedback.hip -- the gait planner's foot-placement feedback (include/wbc_gait_feedback.h): kernel and C ABI.
 //
 // wbc_gait_feedback_kernel runs after whichever gait kernel wrote the targets, on the same stream, in the gait's mapping: a quad of
 // lanes per robot, one foot per lane, 16 robots per wavefront, the packed stride table staged in LDS.  Every lane loads its foot's
@@ -9,20 +9,18 @@
 // wbc_gait_targets_kernel.  No private array is indexed by a run-time value: no scratch.
 //
 // A translation unit of its own, like the schedules': the device code of wbc_gait.hip and wbc_gait_schedule.hip stays what it is.
+// The state lives in the gait handle (wbc_gait_handle.hpp).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/wbc.h"
-#include "wbc_gait_feedback.h"   // include_gait_feedback/: on the include path (build())
+#include "../../include/wbc_gait_feedback.h"
 #include "wbc_gait_feedback.hpp"
+#include "wbc_gait_handle.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
-
-// wbc_gait.hip (internal): what this file needs of a handle
-extern "C" int wbc_gait_feedback_slot_(wbc_gait g, int* device, int* count, int* terrain_count, const double** table, const uint8_t** gait_id,
-                                       const double** scale, wbc::GaitFeedbackState*** slot);
 
 namespace {
 
@@ -111,30 +109,8 @@ __global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_feedback_kernel(Feed
   }
 }
 
-namespace wbc {
-
-void gait_feedback_free(GaitFeedbackState* s) {
-  if (!s) return;
-  if (s->d_state) (void)hipFree(s->d_state);
-  delete s;
-}
-
-}  // namespace wbc
-
 namespace {
 
-struct Handle {
-  int device, count, terrain_count;
-  const double* table;
-  const uint8_t* gait_id;
-  const double* scale;
-  wbc::GaitFeedbackState** slot;
-};
-Handle handle_of(wbc_gait g) {
-  Handle h;
-  wbc_gait_feedback_slot_(g, &h.device, &h.count, &h.terrain_count, &h.table, &h.gait_id, &h.scale, &h.slot);
-  return h;
-}
 size_t state_doubles(int n) { return (size_t)wbc::GAIT_FEEDBACK_ROWS * 4 * (size_t)n; }
 
 }  // namespace
@@ -162,40 +138,32 @@ int wbc_gait_set_feedback(wbc_gait g, const wbc_gait_feedback_params* params, in
   const char* what = wbc::gait_feedback_error(params);
   if (what) return wbc::misuse("wbc_gait_set_feedback", what);
   if (n < 1 || n > WBC_MAX_LD) return wbc::misuse("wbc_gait_set_feedback: n out of range (1 .. WBC_MAX_LD)");
-  const Handle h = handle_of(g);
-  WBC_ON_DEVICE(h.device, wbc::fail);
-  if (!*h.slot) *h.slot = new wbc::GaitFeedbackState();
-  wbc::GaitFeedbackState* s = *h.slot;
+  WBC_ON_DEVICE(g->device, wbc::fail);
   HIP_TRY(hipDeviceSynchronize());   // a launch still working on the state
-  const int had = s->n;
-  s->n = 0;
-  if (s->d_state && had != n) {
-    (void)hipFree(s->d_state);
-    s->d_state = nullptr;
+  const int had = g->feedback_n;
+  g->feedback_n = 0;
+  if (g->d_feedback && had != n) {
+    (void)hipFree(g->d_feedback);
+    g->d_feedback = nullptr;
   }
   const size_t bytes = state_doubles(n) * sizeof(double);
-  if (!s->d_state) HIP_TRY(hipMalloc(&s->d_state, bytes + (size_t)n));
-  HIP_TRY(hipMemset(s->d_state, 0, bytes));
-  HIP_TRY(hipMemset(s->d_state + state_doubles(n), 0x0F, (size_t)n));
+  if (!g->d_feedback) HIP_TRY(hipMalloc(&g->d_feedback, bytes + (size_t)n));
+  HIP_TRY(hipMemset(g->d_feedback, 0, bytes));
+  HIP_TRY(hipMemset(g->d_feedback + state_doubles(n), 0x0F, (size_t)n));
   HIP_TRY(hipDeviceSynchronize());
-  s->par = *params;
-  s->n = n;
+  g->feedback = *params;
+  g->feedback_n = n;
   return 0;
 }
 
 int wbc_gait_clear_feedback(wbc_gait g) {
   if (!g) return wbc::misuse("wbc_gait_clear_feedback: null gait handle");
-  const Handle h = handle_of(g);
-  wbc::GaitFeedbackState* s = *h.slot;
-  if (!s) return 0;
-  *h.slot = nullptr;
-  if (s->d_state) {
-    WBC_ON_DEVICE(h.device, wbc::fail);
-    (void)hipDeviceSynchronize();   // a launch still working on the state
-    wbc::gait_feedback_free(s);
-  } else {
-    delete s;
-  }
+  g->feedback_n = 0;
+  if (!g->d_feedback) return 0;
+  WBC_ON_DEVICE(g->device, wbc::fail);
+  (void)hipDeviceSynchronize();   // a launch still working on the state
+  (void)hipFree(g->d_feedback);
+  g->d_feedback = nullptr;
   return 0;
 }
 
@@ -204,20 +172,18 @@ int wbc_gait_targets_measured(wbc_gait g, void* hip_stream, int n, int ld, const
   const int rc = wbc::plant_check_batch("wbc_gait_targets_measured", g, "gait", n, ld, time && q && v && targets && contact_mask,
                                         "time, q, v, targets and contact_mask");
   if (rc) return rc;
-  const Handle h = handle_of(g);
-  if (!h.table) return wbc::misuse("wbc_gait_targets_measured: wbc_gait_set_commands has not been called on this handle");
-  if (h.terrain_count > 0)
+  if (!g->cmd || !g->d_table) return wbc::misuse("wbc_gait_targets_measured: wbc_gait_set_commands has not been called on this handle");
+  if (g->terrain.count > 0)
     return wbc::misuse("wbc_gait_targets_measured: the handle has a terrain set: the feedback knows no terrain (wbc_gait_feedback.h, limits)");
-  const wbc::GaitFeedbackState* s = *h.slot;
-  if (!wbc::gait_feedback_on(s)) return wbc::misuse("wbc_gait_targets_measured: wbc_gait_set_feedback has not been called on this handle");
-  if (n > s->n) return wbc::misuse("wbc_gait_targets_measured: n is larger than the n of the handle's wbc_gait_set_feedback");
+  if (!wbc::gait_feedback_on(*g)) return wbc::misuse("wbc_gait_targets_measured: wbc_gait_set_feedback has not been called on this handle");
+  if (n > g->feedback_n) return wbc::misuse("wbc_gait_targets_measured: n is larger than the n of the handle's wbc_gait_set_feedback");
   const int rg = wbc_gait_targets(g, hip_stream, n, ld, time, targets, contact_mask);
   if (rg || n == 0) return rg;
-  WBC_ON_DEVICE(h.device, wbc::fail);
+  WBC_ON_DEVICE(g->device, wbc::fail);
   FeedbackArgs a;
-  a.n = n; a.ld = ld; a.count = h.count; a.row = 4 * (size_t)s->n; a.table = h.table; a.time = time; a.gait_id = h.gait_id;
-  a.scale = h.scale; a.q = q; a.v = v; a.targets = targets; a.mask = contact_mask; a.offsets = offsets; a.state = s->d_state;
-  a.prev = (uint8_t*)(s->d_state + state_doubles(s->n)); a.par = s->par;
+  a.n = n; a.ld = ld; a.count = g->count; a.row = 4 * (size_t)g->feedback_n; a.table = g->d_table; a.time = time; a.gait_id = g->gait_id;
+  a.scale = g->scale; a.q = q; a.v = v; a.targets = targets; a.mask = contact_mask; a.offsets = offsets; a.state = g->d_feedback;
+  a.prev = (uint8_t*)(g->d_feedback + state_doubles(g->feedback_n)); a.par = g->feedback;
   hipLaunchKernelGGL(wbc_gait_feedback_kernel, wbc::plant_grid(n), dim3(wbc::QUAD_BLOCK), 0, (hipStream_t)hip_stream, a);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -225,21 +191,20 @@ int wbc_gait_targets_measured(wbc_gait g, void* hip_stream, int n, int ld, const
 
 int wbc_gait_feedback_kernel_info(wbc_gait g, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
   if (!g) return wbc::misuse("wbc_gait_feedback_kernel_info: null gait handle");
-  return WBC_PLANT_KERNEL_INFO(handle_of(g).device, wbc_gait_feedback_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
+  return WBC_PLANT_KERNEL_INFO(g->device, wbc_gait_feedback_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
 }
 
 // internal (not in the header; the tests' read-back): the state of instances 0 .. n-1 to host memory, state [6][4 n] in the layout of
 // wbc_gait_feedback.hpp with n as its capacity, prev [n].  Synchronises the device.
 int wbc_gait_feedback_state_(wbc_gait g, int n, double* state, uint8_t* prev) {
   if (!g || !state || !prev) return wbc::misuse("wbc_gait_feedback_state_: null argument");
-  const Handle h = handle_of(g);
-  const wbc::GaitFeedbackState* s = *h.slot;
-  if (!wbc::gait_feedback_on(s) || n < 1 || n > s->n) return wbc::misuse("wbc_gait_feedback_state_: no feedback set, or n out of range");
-  WBC_ON_DEVICE(h.device, wbc::fail);
+  const int cap = g->feedback_n;
+  if (!wbc::gait_feedback_on(*g) || n < 1 || n > cap) return wbc::misuse("wbc_gait_feedback_state_: no feedback set, or n out of range");
+  WBC_ON_DEVICE(g->device, wbc::fail);
   HIP_TRY(hipDeviceSynchronize());
   for (int r = 0; r < wbc::GAIT_FEEDBACK_ROWS; r++)
-    HIP_TRY(hipMemcpy(state + (size_t)r * 4 * n, s->d_state + (size_t)r * 4 * s->n, (size_t)4 * n * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(prev, s->d_state + state_doubles(s->n), (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(state + (size_t)r * 4 * n, g->d_feedback + (size_t)r * 4 * cap, (size_t)4 * n * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(prev, g->d_feedback + state_doubles(cap), (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }
 

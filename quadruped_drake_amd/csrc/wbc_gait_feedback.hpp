@@ -1,4 +1,4 @@
-// wbc_gait_feedback.hpp -- the gait planner's foot-placement feedback (include_gait_feedback/wbc_gait_feedback.h, "The law"; product
+// wbc_gait_feedback.hpp -- the gait planner's foot-placement feedback (include/wbc_gait_feedback.h, "The law"; product
 // code): its one text, instantiated by wbc_gait_feedback_kernel (wbc_gait_feedback.hip, a quad of lanes per robot, one foot per lane)
 // and by tools/host_gait_feedback.cpp.  The clock and the packed stride are wbc_gait.hpp's, read and not edited.
 //
@@ -10,7 +10,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "wbc_gait_feedback.h"   // include_gait_feedback/: on the include path (build())
+#include "../../include/wbc_gait_feedback.h"
 #include "wbc_gait.hpp"
 
 namespace wbc {
@@ -77,15 +77,5 @@ WBC_HD GaitClock gait_feedback_clock(const double* table, int count, double time
   in.cx = 0.0; in.cy = 0.0; in.w = 0.0; in.x0 = 0.0; in.y0 = 0.0; in.psi0 = 0.0;
   return gait_clock(table, count, in);
 }
-
-// ---------------------------------------------------------------- host: what wbc_gait.hip and wbc_gait_feedback.hip share
-struct GaitFeedbackState {
-  wbc_gait_feedback_params par;
-  int n;             // instances; 0: no feedback
-  double* d_state;   // GAIT_FEEDBACK_ROWS rows of 4 n doubles, then n bytes: the previous masks
-};
-inline bool gait_feedback_on(const GaitFeedbackState* s) { return s && s->n > 0; }
-// the current device is the handle's and idle (wbc_gait_feedback.hip)
-void gait_feedback_free(GaitFeedbackState* s);
 
 }  // namespace wbc

@@ -1,4 +1,4 @@
-// wbc_gait_schedule.hip -- the gait planner's command schedules (include_gait_schedule/wbc_gait_schedule.h): kernels and C ABI.
+// wbc_gait_schedule.hip -- the gait planner's command schedules (include/wbc_gait_schedule.h): kernels and C ABI.
 //
 // wbc_gait_schedule_resolve_kernel, one thread per robot, turns a robot's switches into its rows of the handle's buffer once per
 // wbc_gait_set_schedule (wbc_gait.hpp: gait_schedule_resolve): per switch its Theta, S_j, c_j and the blend's three quintics.
@@ -10,21 +10,19 @@
 // indexed by a run-time value: no scratch.
 //
 // This is a translation unit of its own so that the device code of wbc_gait.hip stays what it is: a handle without a schedule
-// launches that file's kernels, and this file's are reached through wbc_gait_schedule_dev.hpp only while a schedule is set.
+// launches that file's kernels, and this file's are reached through gait_schedule_launch (wbc_gait_handle.hpp) only while a schedule
+// is set.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/wbc.h"
-#include "wbc_gait_schedule.h"   // include_gait_schedule/: on the include path (build())
+#include "../../include/wbc_gait_schedule.h"
 #include "wbc_gait.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
-#include "wbc_gait_schedule_dev.hpp"
-
-// wbc_gait.hip (internal)
-extern "C" int wbc_gait_schedule_slot_(wbc_gait g, int* device, const double** cmd, const double** start, wbc::GaitScheduleState*** slot);
+#include "wbc_gait_handle.hpp"
 
 namespace {
 
@@ -35,7 +33,7 @@ __device__ __forceinline__ void stage(double* dst, const double* src, int words)
 }
 
 // lane l's nine foot rows, and from lane 0 the body rows and the mask
-__device__ __forceinline__ void store(const wbc::GaitLaunch& a, size_t i, int l, const double* f, const double* b, unsigned mask) {
+__device__ __forceinline__ void store(const wbc::GaitArgs& a, size_t i, int l, const double* f, const double* b, unsigned mask) {
   const size_t ld = (size_t)a.ld;
   double* out = a.targets + i;
 #pragma unroll
@@ -49,7 +47,8 @@ __device__ __forceinline__ void store(const wbc::GaitLaunch& a, size_t i, int l,
 
 }  // namespace
 
-__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_schedule_targets_kernel(wbc::GaitLaunch a, wbc::GaitScheduleArgs sa) {
+// both target kernels take the launch, the handle's terrain and its schedule; this one, on the plane, does not read the terrain
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_schedule_targets_kernel(wbc::GaitArgs a, wbc::GaitTerrainArgs, wbc::GaitScheduleArgs sa) {
   using namespace wbc;
   __shared__ double lds[GAIT_TABLE_DOUBLES];
   stage(lds, a.table, GAIT_HEAD + a.count * GAIT_STRIDE);   // count <= WBC_GAIT_MAX_STRIDES: checked by wbc_gait_create
@@ -69,23 +68,23 @@ __global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_schedule_targets_ker
   if (live) store(a, i, l, f, b, c.mask);
 }
 
-__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_schedule_terrain_targets_kernel(wbc::GaitLaunch a, wbc::GaitScheduleArgs sa) {
+__global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_schedule_terrain_targets_kernel(wbc::GaitArgs a, wbc::GaitTerrainArgs ta, wbc::GaitScheduleArgs sa) {
   using namespace wbc;
   __shared__ double lds[GAIT_TABLE_DOUBLES + GAIT_TERRAIN_DOUBLES];
   double* const ter = lds + GAIT_TABLE_DOUBLES;
   stage(lds, a.table, GAIT_HEAD + a.count * GAIT_STRIDE);                // count <= WBC_GAIT_MAX_STRIDES: checked by wbc_gait_create
-  stage(ter, a.ttable, GAIT_TERRAIN_HEAD + a.tcount * TERRAIN_STRIDE);   // tcount <= TERRAIN_MAX_PROFILES: checked by wbc_gait_set_terrain
+  stage(ter, ta.table, GAIT_TERRAIN_HEAD + ta.count * TERRAIN_STRIDE);   // count <= TERRAIN_MAX_PROFILES: checked by wbc_gait_set_terrain
   const int t = blockIdx.x * QUAD_BLOCK + threadIdx.x;
   const int l = t & 3;
   const int r = t >> 2;
   const bool live = r < a.n;
   const size_t i = (size_t)(live ? r : a.n - 1);   // quads past the batch compute on its last robot and store nothing; a.n <= sa.n
   const GaitIn in = gait_load(a.time, a.cmd, a.gait_id, a.scale, a.start, (size_t)a.ld, i);
-  const int tid = a.tid ? (int)a.tid[i] : 0;
-  const double tsc = a.tscale ? a.tscale[i] : 1.0;
+  const int tid = ta.id ? (int)ta.id[i] : 0;
+  const double tsc = ta.scale ? ta.scale[i] : 1.0;
   const GaitSchedule S = gait_schedule_load(sa.knots, (size_t)sa.ld, i, sa.beta);
   __syncthreads();
-  const GaitGround G = gait_ground(ter, a.tcount, tid, tsc);
+  const GaitGround G = gait_ground(ter, ta.count, tid, tsc);
   GaitClock c = gait_clock(lds, a.count, in);
   gait_clock_spoil(c, G.bad | S.bad);
   double b[18], f[9], own[3], gr[12];
@@ -118,19 +117,13 @@ __global__ void __launch_bounds__(wbc::QUAD_BLOCK) wbc_gait_schedule_resolve_ker
 
 namespace wbc {
 
-int gait_schedule_launch(const GaitScheduleState* s, void* hip_stream, const GaitLaunch& L) {
-  if (L.tcount > 0)
-    hipLaunchKernelGGL(wbc_gait_schedule_terrain_targets_kernel, plant_grid(L.n), dim3(QUAD_BLOCK), 0, (hipStream_t)hip_stream, L, s->args);
+int gait_schedule_launch(const wbc_gait_s& g, void* hip_stream, const GaitArgs& a) {
+  if (g.terrain.count > 0)
+    hipLaunchKernelGGL(wbc_gait_schedule_terrain_targets_kernel, plant_grid(a.n), dim3(QUAD_BLOCK), 0, (hipStream_t)hip_stream, a, g.terrain, g.schedule);
   else
-    hipLaunchKernelGGL(wbc_gait_schedule_targets_kernel, plant_grid(L.n), dim3(QUAD_BLOCK), 0, (hipStream_t)hip_stream, L, s->args);
+    hipLaunchKernelGGL(wbc_gait_schedule_targets_kernel, plant_grid(a.n), dim3(QUAD_BLOCK), 0, (hipStream_t)hip_stream, a, g.terrain, g.schedule);
   HIP_TRY(hipGetLastError());
   return 0;
-}
-
-void gait_schedule_free(GaitScheduleState* s) {
-  if (!s) return;
-  if (s->d_knots) (void)hipFree(s->d_knots);
-  delete s;
 }
 
 }  // namespace wbc
@@ -146,50 +139,36 @@ int wbc_gait_set_schedule(wbc_gait g, void* hip_stream, int n, int ld, double bl
   if (n < 1 || n > WBC_MAX_LD) return wbc::misuse("wbc_gait_set_schedule: n out of range (1 .. WBC_MAX_LD)");
   if (ld > WBC_MAX_LD) return wbc::misuse("wbc_gait_set_schedule: ld exceeds WBC_MAX_LD");
   if (ld < n) return wbc::misuse("wbc_gait_set_schedule: ld must be >= n");
-  int device;
-  const double *cmd, *start;
-  wbc::GaitScheduleState** slot;
-  wbc_gait_schedule_slot_(g, &device, &cmd, &start, &slot);
-  if (!cmd) return wbc::misuse("wbc_gait_set_schedule: wbc_gait_set_commands has not been called on this handle");
-  WBC_ON_DEVICE(device, wbc::fail);
-  if (!*slot) *slot = new wbc::GaitScheduleState();
-  wbc::GaitScheduleState* s = *slot;
-  s->args = wbc::GaitScheduleArgs{};
-  if (s->capacity < ld) {
+  if (!g->cmd || !g->d_table) return wbc::misuse("wbc_gait_set_schedule: wbc_gait_set_commands has not been called on this handle");
+  WBC_ON_DEVICE(g->device, wbc::fail);
+  g->schedule = wbc::GaitScheduleArgs{};
+  if (g->knots_capacity < ld) {
     HIP_TRY(hipDeviceSynchronize());   // a launch still reading the previous buffer
-    if (s->d_knots) (void)hipFree(s->d_knots);
-    s->d_knots = nullptr;
-    s->capacity = 0;
-    HIP_TRY(hipMalloc(&s->d_knots, (size_t)wbc::GAIT_SCHEDULE_ROWS * (size_t)ld * sizeof(double)));
-    s->capacity = ld;
+    if (g->d_knots) (void)hipFree(g->d_knots);
+    g->d_knots = nullptr;
+    g->knots_capacity = 0;
+    HIP_TRY(hipMalloc(&g->d_knots, (size_t)wbc::GAIT_SCHEDULE_ROWS * (size_t)ld * sizeof(double)));
+    g->knots_capacity = ld;
   }
   const unsigned blocks = (unsigned)((n + wbc::QUAD_BLOCK - 1) / wbc::QUAD_BLOCK);
-  hipLaunchKernelGGL(wbc_gait_schedule_resolve_kernel, dim3(blocks), dim3(wbc::QUAD_BLOCK), 0, (hipStream_t)hip_stream, n, ld, blend, cmd, start,
-                     nswitch, when, cmds, s->d_knots);
+  hipLaunchKernelGGL(wbc_gait_schedule_resolve_kernel, dim3(blocks), dim3(wbc::QUAD_BLOCK), 0, (hipStream_t)hip_stream, n, ld, blend, g->cmd,
+                     g->start, nswitch, when, cmds, g->d_knots);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));   // the caller may free its arrays
-  s->args.n = n; s->args.ld = ld; s->args.beta = blend; s->args.knots = s->d_knots;
+  g->schedule.n = n; g->schedule.ld = ld; g->schedule.beta = blend; g->schedule.knots = g->d_knots;
   return 0;
 }
 
 int wbc_gait_clear_schedule(wbc_gait g) {
   if (!g) return wbc::misuse("wbc_gait_clear_schedule: null gait handle");
-  int device;
-  const double *cmd, *start;
-  wbc::GaitScheduleState** slot;
-  wbc_gait_schedule_slot_(g, &device, &cmd, &start, &slot);
-  if (*slot) (*slot)->args = wbc::GaitScheduleArgs{};
+  g->schedule = wbc::GaitScheduleArgs{};   // the buffer stays for the next wbc_gait_set_schedule
   return 0;
 }
 
 int wbc_gait_schedule_kernel_info(wbc_gait g, int terrain, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads) {
   if (!g) return wbc::misuse("wbc_gait_schedule_kernel_info: null gait handle");
-  int device;
-  const double *cmd, *start;
-  wbc::GaitScheduleState** slot;
-  wbc_gait_schedule_slot_(g, &device, &cmd, &start, &slot);
-  if (terrain) return WBC_PLANT_KERNEL_INFO(device, wbc_gait_schedule_terrain_targets_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
-  return WBC_PLANT_KERNEL_INFO(device, wbc_gait_schedule_targets_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
+  if (terrain) return WBC_PLANT_KERNEL_INFO(g->device, wbc_gait_schedule_terrain_targets_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
+  return WBC_PLANT_KERNEL_INFO(g->device, wbc_gait_schedule_targets_kernel, num_vgpr, scratch_bytes, lds_bytes, block_threads);
 }
 
 }  // extern "C"

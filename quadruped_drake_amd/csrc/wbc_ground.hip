@@ -15,16 +15,14 @@
 #include "../../include/wbc.h"
 #include "../../include/wbc_ground.h"
 #include "../../include/wbc_gait.h"
-#include "wbc_gait_feedback.h"   // include_gait_feedback/: on the include path (build())
+#include "../../include/wbc_gait_feedback.h"
 #include "wbc_model.hpp"
 #include "wbc_tick.hpp"
 #include "wbc_ground.hpp"
 #include "wbc_ground_follow.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
-
-extern "C" int wbc_gait_device_(wbc_gait g);   // wbc_gait.hip (internal): the device a gait handle was created for
-extern "C" int wbc_gait_feedback_on_(wbc_gait g);   // wbc_gait.hip (internal): whether wbc_gait_set_feedback holds on the handle
+#include "wbc_gait_handle.hpp"   // host only: the device of a gait handle, and whether feedback is set on it
 
 namespace {
 
@@ -406,7 +404,7 @@ int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stre
   const bool follow = g->follow != WBC_FOLLOW_OFF && g->terrain.count > 0;   // otherwise: the launches of a rollout without it
   // the tick's targets: the gait's while one is set, else the lookup in `traj` -- the launch a rollout without a gait issues.  A
   // gait with feedback set (wbc_gait_feedback.h) reads the rollout's own q and v: one more launch per tick.
-  const bool measured = g->gait && wbc_gait_feedback_on_(g->gait);
+  const bool measured = g->gait && wbc::gait_feedback_on(*g->gait);
   auto source = [&](wbc_traj tr, void* s, int n_, int ld_, const double* t, double* tg, uint8_t* m) {
     if (measured) return wbc_gait_targets_measured(g->gait, s, n_, ld_, t, q, v, tg, m, nullptr);
     return g->gait ? wbc_gait_targets(g->gait, s, n_, ld_, t, tg, m) : wbc_traj_lookup(tr, s, n_, ld_, t, tg, m);
@@ -418,7 +416,7 @@ int wbc_ground_rollout(wbc_handle h, wbc_ground g, wbc_traj traj, void* hip_stre
 
 int wbc_ground_set_gait(wbc_ground g, wbc_gait gait) {
   if (!g) return wbc::misuse("wbc_ground_set_gait: null ground handle");
-  if (gait && wbc_gait_device_(gait) != g->device) return wbc::misuse("wbc_ground_set_gait: the gait handle lives on another device than the plant");
+  if (gait && gait->device != g->device) return wbc::misuse("wbc_ground_set_gait: the gait handle lives on another device than the plant");
   g->gait = gait;
   return 0;
 }

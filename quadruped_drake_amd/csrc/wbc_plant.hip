@@ -13,15 +13,13 @@
 #include "../../include/wbc.h"
 #include "../../include/wbc_plant.h"
 #include "../../include/wbc_gait.h"
-#include "wbc_gait_feedback.h"   // include_gait_feedback/: on the include path (build())
+#include "../../include/wbc_gait_feedback.h"
 #include "wbc_model.hpp"
 #include "wbc_tick.hpp"
 #include "wbc_plant.hpp"
 #include "wbc_quad.hpp"
 #include "wbc_plant_host.hpp"
-
-extern "C" int wbc_gait_device_(wbc_gait g);   // wbc_gait.hip (internal): the device a gait handle was created for
-extern "C" int wbc_gait_feedback_on_(wbc_gait g);   // wbc_gait.hip (internal): whether wbc_gait_set_feedback holds on the handle
+#include "wbc_gait_handle.hpp"   // host only: the device of a gait handle, and whether feedback is set on it
 
 namespace {
 
@@ -333,7 +331,7 @@ int wbc_plant_rollout(wbc_handle h, wbc_plant p, wbc_traj traj, void* hip_stream
   const PlantArgs a = make_args(p, n, ld, dt, q, v, time, tau, contact_mask, plant_mu, plant_mass_scale, nullptr, force, flags, counts);
   // the tick's targets: the gait's while one is set, else the lookup in `traj` -- the launch a rollout without a gait issues.  A
   // gait with feedback set (wbc_gait_feedback.h) reads the rollout's own q and v: one more launch per tick.
-  const bool measured = p->gait && wbc_gait_feedback_on_(p->gait);
+  const bool measured = p->gait && wbc::gait_feedback_on(*p->gait);
   auto source = [&](wbc_traj tr, void* s, int n_, int ld_, const double* t, double* tg, uint8_t* m) {
     if (measured) return wbc_gait_targets_measured(p->gait, s, n_, ld_, t, q, v, tg, m, nullptr);
     return p->gait ? wbc_gait_targets(p->gait, s, n_, ld_, t, tg, m) : wbc_traj_lookup(tr, s, n_, ld_, t, tg, m);
@@ -345,7 +343,7 @@ int wbc_plant_rollout(wbc_handle h, wbc_plant p, wbc_traj traj, void* hip_stream
 
 int wbc_plant_set_gait(wbc_plant p, wbc_gait gait) {
   if (!p) return wbc::misuse("wbc_plant_set_gait: null plant handle");
-  if (gait && wbc_gait_device_(gait) != p->device) return wbc::misuse("wbc_plant_set_gait: the gait handle lives on another device than the plant");
+  if (gait && gait->device != p->device) return wbc::misuse("wbc_plant_set_gait: the gait handle lives on another device than the plant");
   p->gait = gait;
   return 0;
 }

@@ -8,9 +8,9 @@ and its own stride period, and no table of samples.  `plant.closed_loop` takes a
 `GaitPlanner.set_terrain` gives the planner the plant's terrain (include/wbc_gait_terrain.h): its targets are then the
 finished targets on that ground -- footholds off the risers, swings that clear the knots, a body that follows the feet -- and no
 follow pass runs after them.
-`GaitPlanner.set_schedule` steers it (include_gait_schedule/wbc_gait_schedule.h): every robot walks its own sequence of commands,
+`GaitPlanner.set_schedule` steers it (include/wbc_gait_schedule.h): every robot walks its own sequence of commands,
 switched at its own times and joined by smooth turns -- up to a kerb and along it, a square, to a stop, into reverse.
-`GaitPlanner.set_feedback` closes the loop on the footholds (include_gait_feedback/wbc_gait_feedback.h): a pass after the gait's kernel
+`GaitPlanner.set_feedback` closes the loop on the footholds (include/wbc_gait_feedback.h): a pass after the gait's kernel
 shifts every swing's landing point by what the measured trunk velocity asks for, so that a pushed robot steps after its trunk.
 Torch tensors and torch's current stream, as in controller.py and plant.py.
 """
@@ -170,7 +170,7 @@ class GaitPlanner:
         self._n, self._keep = n, (cmd, gait_id, stride_scale, start)
 
     def set_schedule(self, times, cmds, blend=0.5):
-        """Steer the planner (include_gait_schedule/wbc_gait_schedule.h): from times[j] [s after wait_time] on a robot walks cmds[j]
+        """Steer the planner (include/wbc_gait_schedule.h): from times[j] [s after wait_time] on a robot walks cmds[j]
         instead of the command before it, the first being set_commands' cmd.  times: [M] or [M, N], M <= 7, each at or after
         ramp_time, +inf from a robot's last switch on; cmds: [M, 3] or [M, 3, N]; numpy or lists, one column per robot or one for
         all.  blend [s of steady walking]: the length of the smooth turn after a switch, which must end before the next switch
@@ -208,7 +208,7 @@ class GaitPlanner:
         return dict(k_v=p.k_v, k_p=p.k_p, d_max=p.d_max, u_hold=p.u_hold)
 
     def set_feedback(self, n, **params):
-        """Let the footholds react to the measured trunk (include_gait_feedback/wbc_gait_feedback.h): allocates and zeroes the state
+        """Let the footholds react to the measured trunk (include/wbc_gait_feedback.h): allocates and zeroes the state
         of n robots; called again, it resets it.  params: k_v [s], k_p, d_max [m], u_hold over feedback_defaults().  From then on
         targets_measured() works, and a rollout that takes this planner (plant.closed_loop) feeds it its own q and v; targets() is
         unchanged.  Not with a terrain.  Synchronises the device."""

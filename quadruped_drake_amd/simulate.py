@@ -26,13 +26,13 @@ WALK: gait.GaitPlanner computes each tick's targets on the device from a velocit
 backwards or climbs a slope of grade 0.2, and walks all of them at half that period (profiles/r13/gait.md, gait_sweep.md).  With
 `--plant ground` the result line also has the mean and the worst distance of the trunks from their planned (x, y).
 `--cmd-schedule "T:VX,VY,WZ;..." [--cmd-blend B]` (with `--planner gait`) steers every robot: from T seconds on it walks VX,VY,WZ, with a
-smooth turn of length B (default 0.5) after each of up to seven switches (include_gait_schedule/wbc_gait_schedule.h); `--cmd-spread`
+smooth turn of length B (default 0.5) after each of up to seven switches (include/wbc_gait_schedule.h); `--cmd-spread`
 spreads the first command only.
 `--gait-terrain lift|fit` (with `--planner gait` and `--terrain`; default `off`; excludes `--follow`) gives the plant's terrain to the
 planner (include/wbc_gait_terrain.h): footholds on the surface and off the risers, swings that clear what lies between
 their footholds, a body that follows the feet (`fit`: also in pitch and roll).  That is what walks a kerb of 0.1 m.
 `--gait-feedback [KV,KP,DMAX,UHOLD]` (with `--planner gait`, without `--gait-terrain`) lets the footholds react to the measured trunk
-(include_gait_feedback/wbc_gait_feedback.h): a velocity gain [s], a position gain, the largest offset [m] and the swing fraction up to
+(include/wbc_gait_feedback.h): a velocity gain [s], a position gain, the largest offset [m] and the swing fraction up to
 which a landing point still moves; without a value, wbc_gait_feedback_params_default's.  `--push T0:T1:FX,FY` (with `--plant ground`)
 applies the world force FX,FY [N] to every trunk during [T0, T1) seconds, by splitting the rollout into calls at T0 and T1."""
 import argparse

@@ -1,5 +1,5 @@
 """The gait planner's foot-placement feedback restated in numpy from the sentences at the head of
-include_gait_feedback/wbc_gait_feedback.h (tests only; shares no code with csrc/ and takes its clock from gait_oracle).  The state is
+include/wbc_gait_feedback.h (tests only; shares no code with csrc/ and takes its clock from gait_oracle).  The state is
 carried from call to call in a State; every function takes `dtype`: np.float64, or np.longdouble for the extended-precision answer
 the CPU tests measure their bars with."""
 import numpy as np

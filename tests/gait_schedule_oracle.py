@@ -1,5 +1,5 @@
 """The gait planner's command schedules restated in numpy from the sentences at the head of
-include_gait_schedule/wbc_gait_schedule.h (tests only; shares no code with csrc/wbc_gait.hpp and knows nothing of its buffer of
+include/wbc_gait_schedule.h (tests only; shares no code with csrc/wbc_gait.hpp and knows nothing of its buffer of
 resolved switches).  That header changes one thing, the body's pose function P(theta); what it leaves as it is -- the clock, the
 runs, the swings, the terrain law -- is gait_oracle.py's and gait_terrain_oracle.py's restatement, evaluated with their `pose`
 replaced by P.  Every function takes `dtype`: np.float64, or np.longdouble for the extended-precision answer the tests measure their

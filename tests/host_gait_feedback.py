@@ -1,5 +1,5 @@
 """ctypes view of host_gait_feedback_batch of tools/libhost_gait.so: the gait planner's foot-placement feedback
-(include_gait_feedback/wbc_gait_feedback.h), csrc/wbc_gait_feedback.hpp instantiated on the host (tests only).  The caller holds the
+(include/wbc_gait_feedback.h), csrc/wbc_gait_feedback.hpp instantiated on the host (tests only).  The caller holds the
 state, in the device's layout, in a State."""
 import ctypes as C
 

@@ -1,5 +1,5 @@
 """ctypes view of host_gait_schedule_batch of tools/libhost_gait.so: the gait planner's law under command schedules
-(include_gait_schedule/wbc_gait_schedule.h), the SCHEDULE instantiations of csrc/wbc_gait.hpp on the host (tests only).  run() takes the
+(include/wbc_gait_schedule.h), the SCHEDULE instantiations of csrc/wbc_gait.hpp on the host (tests only).  run() takes the
 planner as host_gait.run takes it, the schedule as wbc_gait_set_schedule does, an optional terrain as host_gait_terrain.run does, and
 numpy arrays."""
 import ctypes as C

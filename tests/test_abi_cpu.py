@@ -29,11 +29,12 @@ def test_library_loads_and_exports_every_declared_symbol():
 _MIRRORS = {"wbc_model": "WbcModel", "wbc_params": "WbcParams", "wbc_stats": "WbcStats", "wbc_trunk_state": "WbcTrunkState",
             "wbc_robot_state": "WbcRobotState", "wbc_plant_params": "WbcPlantParams", "wbc_ground_params": "WbcGroundParams",
             "wbc_terrain_profile": "WbcTerrainProfile", "wbc_gait_stride": "WbcGaitStride", "wbc_gait_params": "WbcGaitParams",
-            "wbc_gait_terrain_params": "WbcGaitTerrainParams"}
+            "wbc_gait_terrain_params": "WbcGaitTerrainParams", "wbc_gait_feedback_params": "WbcGaitFeedbackParams"}
 _BY_VALUE = {"int": C.c_int, "double": C.c_double, "uint32_t": C.c_uint32, "uint8_t": C.c_uint8, "size_t": C.c_size_t}
 _POINTEE = {"double": C.c_double, "int": C.c_int, "int32_t": C.c_int32, "uint8_t": C.c_uint8}
 _HANDLES = ("wbc_handle", "wbc_traj", "wbc_plant", "wbc_ground", "wbc_gait")
-_HEADERS = ("wbc.h", "wbc_extras.h", "wbc_plant.h", "wbc_ground.h", "wbc_gait.h", "wbc_gait_terrain.h")
+_HEADERS = ("wbc.h", "wbc_extras.h", "wbc_plant.h", "wbc_ground.h", "wbc_gait.h", "wbc_gait_terrain.h", "wbc_gait_schedule.h",
+            "wbc_gait_feedback.h")
 
 
 def _header_prototypes(pattern="*.h"):
@@ -90,6 +91,9 @@ _FOLLOW = ["wbc_ground_follow_kernel_info", "wbc_ground_follow_targets", "wbc_gr
 _GAIT = ["wbc_gait_check", "wbc_gait_create", "wbc_gait_destroy", "wbc_gait_kernel_info", "wbc_gait_set_commands", "wbc_gait_targets",
          "wbc_ground_set_gait", "wbc_plant_set_gait"]
 _GAIT_TERRAIN = ["wbc_gait_set_terrain", "wbc_gait_terrain_check", "wbc_gait_terrain_kernel_info"]
+_GAIT_SCHEDULE = ["wbc_gait_clear_schedule", "wbc_gait_schedule_kernel_info", "wbc_gait_set_schedule"]
+_GAIT_FEEDBACK = ["wbc_gait_clear_feedback", "wbc_gait_feedback_check", "wbc_gait_feedback_kernel_info", "wbc_gait_feedback_params_default",
+                  "wbc_gait_set_feedback", "wbc_gait_targets_measured"]
 
 
 def test_prototype_table_equals_the_headers():
@@ -97,23 +101,26 @@ def test_prototype_table_equals_the_headers():
     the return type, the number of arguments and, position by position, the by-value type, pointer-ness and the struct a typed pointer
     points to.  An argument list that is one pointer short or has two positions swapped does not fail on the CPU -- it is a wrong device
     pointer inside a kernel -- so it must not get as far as a GPU.  Needs neither the built library nor a GPU.  The set of entry points is
-    pinned, header by header, and the checker is then shown ten doctored tables and must name the function in each."""
+    pinned, header by header, and the checker is then shown fifteen doctored tables and must name the function in each."""
     from quadruped_drake_amd import _lib
     header = _header_prototypes()
     per = {h: sorted(_header_prototypes(h)) for h in _HEADERS}
     assert sorted(os.listdir(os.path.join(ROOT, "include"))) == sorted(_HEADERS)
-    assert len(header) == 64 == sum(len(v) for v in per.values())
-    assert [len(per[h]) for h in _HEADERS] == [28, 5, 7, 13, 8, 3]
+    assert len(header) == 73 == sum(len(v) for v in per.values())
+    assert [len(per[h]) for h in _HEADERS] == [28, 5, 7, 13, 8, 3, 3, 6]
     assert [n for n in per["wbc_ground.h"] if "follow" in n] == _FOLLOW and per["wbc_gait.h"] == _GAIT and per["wbc_gait_terrain.h"] == _GAIT_TERRAIN
+    assert per["wbc_gait_schedule.h"] == _GAIT_SCHEDULE and per["wbc_gait_feedback.h"] == _GAIT_FEEDBACK
     assert header["wbc_last_error"] == ("char*", []) and header["wbc_integrate"][1][3] == "double"
     assert header["wbc_ground_follow_targets"] == ("int", ["wbc_ground", "void*", "int", "int", "int", "double*"])
     assert header["wbc_gait_targets"] == ("int", ["wbc_gait", "void*", "int", "int", "double*", "double*", "uint8_t*"])
     assert header["wbc_gait_create"] == ("int", ["wbc_gait_params*", "wbc_gait_stride*", "int", "int", "wbc_gait*"])
     assert header["wbc_gait_set_terrain"] == ("int", ["wbc_gait", "wbc_gait_terrain_params*", "wbc_terrain_profile*", "int", "uint8_t*", "double*"])
+    assert header["wbc_gait_set_schedule"] == ("int", ["wbc_gait", "void*", "int", "int", "double", "uint8_t*", "double*", "double*"])
+    assert header["wbc_gait_targets_measured"] == ("int", ["wbc_gait", "void*", "int", "int", "double*", "double*", "double*", "double*", "uint8_t*", "double*"])
     assert _prototype_mismatches(header, _lib.PROTOTYPES, _lib) == []
     assert _lib.SYMBOLS == list(_lib.PROTOTYPES)
-    # what a library under A/B timing may lack on top of the terrain: the statistics exchange and the three newest headers' names
-    assert sorted(_lib._NEWER) == sorted(["wbc_stats_pack", "wbc_stats_reduce"] + _FOLLOW + _GAIT + _GAIT_TERRAIN)
+    # what a library under A/B timing may lack on top of the terrain: the statistics exchange and the five newest headers' names
+    assert sorted(_lib._NEWER) == sorted(["wbc_stats_pack", "wbc_stats_reduce"] + _FOLLOW + _GAIT + _GAIT_TERRAIN + _GAIT_SCHEDULE + _GAIT_FEEDBACK)
     assert set(_lib._MAY_LACK) == {"wbc_terrain_check", "wbc_ground_set_terrain", "wbc_ground_terrain_kernel_info"} | \
         (set(_lib._NEWER) if "WBC_HIP_LIB" in os.environ else set())
 
@@ -128,31 +135,38 @@ def test_prototype_table_equals_the_headers():
     short = [("wbc_ground_rollout", lambda a: a[:-1], "25 arguments in the header, 24"),                 # one pointer dropped
              ("wbc_ground_follow_targets", lambda a: a[:4] + a[5:], "6 arguments in the header, 5"),     # the mode dropped
              ("wbc_gait_targets", lambda a: a[:3] + a[4:], "7 arguments in the header, 6"),              # ld dropped
-             ("wbc_gait_set_terrain", lambda a: a[:3] + a[4:], "6 arguments in the header, 5")]          # count dropped
+             ("wbc_gait_set_terrain", lambda a: a[:3] + a[4:], "6 arguments in the header, 5"),          # count dropped
+             ("wbc_gait_set_schedule", lambda a: a[:4] + a[5:], "8 arguments in the header, 7"),         # the blend dropped
+             ("wbc_gait_targets_measured", lambda a: a[:-1], "10 arguments in the header, 9")]           # the offsets dropped
     for name, change, what in short:
         bad = doctored(name, change)
         assert len(bad) == 1 and bad[0].startswith("%s: %s" % (name, what)), bad
     assert (header["wbc_integrate"][1][2:4], _lib.PROTOTYPES["wbc_integrate"][1][2:4]) == (["int", "double"], [C.c_int, C.c_double])
     swapped = [("wbc_integrate", lambda a: a[:2] + [a[3], a[2]] + a[4:]),                                # dt and ld
                ("wbc_ground_set_follow", lambda a: [C.c_int, C.c_void_p]),                               # handle and mode
-               ("wbc_gait_create", lambda a: [_lib._GAITS, _lib._GAITP] + a[2:])]                        # params and strides
+               ("wbc_gait_create", lambda a: [_lib._GAITS, _lib._GAITP] + a[2:]),                        # params and strides
+               ("wbc_gait_set_schedule", lambda a: a[:3] + [a[4], a[3]] + a[5:])]                        # ld and blend
     for name, change in swapped:
         bad = doctored(name, change)
         assert len(bad) == 2 and all(b.startswith(name + ": argument") for b in bad), bad
-    for name in ("wbc_plant_step", "wbc_plant_set_gait", "wbc_gait_terrain_kernel_info"):               # one function missing
+    for name in ("wbc_plant_step", "wbc_plant_set_gait", "wbc_gait_terrain_kernel_info", "wbc_gait_clear_schedule",
+                 "wbc_gait_feedback_check"):                                                             # one function missing
         assert doctored(name) == [name + ": declared in the headers, missing from the table"]
 
 
 @pytest.mark.parametrize("header,status", [
     ("wbc_ground.h", "WBC_FOLLOW_FIT - 2"),
     ("wbc_gait.h", "(int)sizeof(wbc_gait_stride) - 80 + (int)sizeof(wbc_gait_params) - 96 + WBC_GAIT_MAX_PHASES - 8 + WBC_GAIT_MAX_STRIDES - 16"),
-    ("wbc_gait_terrain.h", "(int)sizeof(wbc_gait_terrain_params) - 32 + WBC_GAIT_BODY_LIFT + WBC_GAIT_BODY_FIT - 1")])
+    ("wbc_gait_terrain.h", "(int)sizeof(wbc_gait_terrain_params) - 32 + WBC_GAIT_BODY_LIFT + WBC_GAIT_BODY_FIT - 1"),
+    ("wbc_gait_schedule.h", "WBC_GAIT_MAX_SWITCHES - 7"),
+    ("wbc_gait_feedback.h", "(int)sizeof(wbc_gait_feedback_params) - 32 + (int)(wbc_gait_feedback_params){0.0, 0.0, 0.1, 0.5}.k_p")])
 def test_the_newer_headers_stand_alone_as_c99(tmp_path, header, status):
     """A C caller includes one header and passes one -I: each compiles alone, pedantically, and the program it makes finds the constants and
     the struct sizes of the ctypes mirrors."""
     import subprocess
-    from quadruped_drake_amd import _lib
+    from quadruped_drake_amd import _lib, gait
     assert (C.sizeof(_lib.WbcGaitStride), C.sizeof(_lib.WbcGaitParams), C.sizeof(_lib.WbcGaitTerrainParams)) == (80, 96, 32)
+    assert C.sizeof(_lib.WbcGaitFeedbackParams) == 32 and gait.MAX_SWITCHES == 7
     src = tmp_path / "alone.c"
     src.write_text('#include "%s"\nint main(void) { return %s; }\n' % (header, status))
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-o",
@@ -296,7 +310,7 @@ def test_dpp_hazard_lint_flags_a_violation_and_passes_clean_code(tmp_path):
 
 
 def test_headers_compile_as_c99_and_struct_layouts_equal_the_ctypes_mirrors(tmp_path):
-    """The six headers of include/ are C headers (`gcc -std=c99 -Wall -pedantic`), and every struct the ctypes
+    """The eight headers of include/ are C headers (`gcc -std=c99 -Wall -pedantic`), and every struct the ctypes
     mirror in quadruped_drake_amd/_lib.py re-declares by hand has the same size and the same offset for every field: a member
     added on one side only would otherwise be a silent mis-read across the boundary."""
     import subprocess

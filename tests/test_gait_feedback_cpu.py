@@ -1,4 +1,4 @@
-"""The gait planner's foot-placement feedback (include_gait_feedback/wbc_gait_feedback.h) without a GPU: the host instantiation of
+"""The gait planner's foot-placement feedback (include/wbc_gait_feedback.h) without a GPU: the host instantiation of
 csrc/wbc_gait_feedback.hpp (tools/host_gait_feedback.cpp through tests/host_gait_feedback.py) against the numpy restatement of the
 header (tests/gait_feedback_oracle.py) in double and in extended precision, the law's exact relations on both, damaged instances,
 what the C ABI refuses before any device is touched, the binding, the twin under the sanitizers as a stand-alone program, and ID
@@ -16,7 +16,6 @@ import gait_oracle as go
 import host_gait as hg
 import host_gait_feedback as hgf
 import host_gait_schedule as hgs
-import test_abi_cpu as abi
 import test_gait_cpu as tgc
 from quadruped_drake_amd import gait, workloads
 
@@ -403,45 +402,12 @@ def test_abi_gait_feedback_misuse_without_device():
     assert g2.feedback_defaults() == gfo.defaults(P["height"]) and not g2.has_feedback
 
 
-FEEDBACK_NAMES = ["wbc_gait_clear_feedback", "wbc_gait_feedback_check", "wbc_gait_feedback_kernel_info", "wbc_gait_feedback_params_default",
-                  "wbc_gait_set_feedback", "wbc_gait_targets_measured"]
-
-
-def test_feedback_prototype_table_equals_its_header(tmp_path):
-    """_lib.PROTOTYPES_FEEDBACK against include_gait_feedback/wbc_gait_feedback.h with the checker of tests/test_abi_cpu.py; the library
-    exports the six names and lib() bound them as the table says; PROTOTYPES and SYMBOLS hold none of them; the directory holds the one
-    file; the header stands alone as C99 with its two include directories."""
-    from quadruped_drake_amd import _lib
-    assert os.listdir(os.path.join(ROOT, "include_gait_feedback")) == ["wbc_gait_feedback.h"]
-    header = abi._header_prototypes(os.path.join("..", "include_gait_feedback", "*.h"))
-    assert sorted(header) == FEEDBACK_NAMES == sorted(_lib.PROTOTYPES_FEEDBACK)
-    assert header["wbc_gait_targets_measured"] == ("int", ["wbc_gait", "void*", "int", "int", "double*", "double*", "double*", "double*", "uint8_t*", "double*"])
-    assert abi._prototype_mismatches(header, _lib.PROTOTYPES_FEEDBACK, _lib) == []
-    assert not set(_lib.PROTOTYPES_FEEDBACK) & (set(_lib.PROTOTYPES) | set(_lib.PROTOTYPES_SCHEDULE) | set(_lib.SYMBOLS))
-    t = dict(_lib.PROTOTYPES_FEEDBACK)
-    res, args = t["wbc_gait_targets_measured"]
-    t["wbc_gait_targets_measured"] = (res, args[:-1])                                           # the offsets dropped
-    bad = abi._prototype_mismatches(header, t, _lib)
-    assert len(bad) == 1 and bad[0].startswith("wbc_gait_targets_measured: 10 arguments in the header, 9"), bad
-    l = _lib.lib()
-    for s in FEEDBACK_NAMES:
-        fn = getattr(l, s)
-        assert fn.restype is _lib.PROTOTYPES_FEEDBACK[s][0] and list(fn.argtypes) == _lib.PROTOTYPES_FEEDBACK[s][1], s
-    assert C.sizeof(_lib.WbcGaitFeedbackParams) == 32
-    src = tmp_path / "alone.c"
-    src.write_text('#include "wbc_gait_feedback.h"\nint main(void) { wbc_gait_feedback_params p = {0.0, 0.0, 0.1, 0.5}; return (int)sizeof p - 32 + (int)p.k_p; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-I",
-                    os.path.join(ROOT, "include_gait_feedback"), "-o", str(tmp_path / "alone"), str(src)], check=True, capture_output=True)
-    assert subprocess.run([str(tmp_path / "alone")]).returncode == 0
-
-
 def test_the_twin_runs_clean_under_the_sanitizers_as_a_stand_alone_program(tmp_path):
     """tools/host_gait_feedback_check.cpp + tools/host_gait_feedback.cpp + tools/host_gait.cpp built with -fsanitize=address,undefined (no
     recovery) and run: a walk of every kind of instance, zero gains, a constant error, damage, arrays exactly as long as the batch."""
     exe = tmp_path / "check"
     subprocess.run(["g++", "-O1", "-g", "-std=c++20", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "include_gait_schedule"), "-I", os.path.join(ROOT, "include_gait_feedback"),
-                    "-o", str(exe), os.path.join(ROOT, "tools", "host_gait_feedback_check.cpp"), os.path.join(ROOT, "tools", "host_gait_feedback.cpp"),
+                    "-I", os.path.join(ROOT, "include"), "-o", str(exe), os.path.join(ROOT, "tools", "host_gait_feedback_check.cpp"), os.path.join(ROOT, "tools", "host_gait_feedback.cpp"),
                     os.path.join(ROOT, "tools", "host_gait.cpp")], check=True, capture_output=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     print(r.stdout, r.stderr)

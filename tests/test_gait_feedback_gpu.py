@@ -1,6 +1,6 @@
-"""The gait planner's foot-placement feedback on the device (include_gait_feedback/wbc_gait_feedback.h): wbc_gait_feedback_kernel against
+"""The gait planner's foot-placement feedback on the device (include/wbc_gait_feedback.h): wbc_gait_feedback_kernel against
 the host twin at the smallest shapes at which the quad mapping can go wrong, the law's exact relations, damaged instances in every
-slot of a wavefront, the kernels' resources, the rollouts with feedback against the launches made by hand, and a batch of pushed
+slot of a wavefront, one handle through every change of its configuration against fresh handles, the kernels' resources, the rollouts with feedback against the launches made by hand, and a batch of pushed
 walks against the host twins.  Measured figures: profiles/r16/gait_feedback.md."""
 import ctypes as C
 import functools
@@ -197,6 +197,105 @@ def test_zero_gains_feedback_set_and_padding_change_no_bit():
     _sync()
     assert (tg[0][:, n:] == FILL).all().item()
     g.close()
+
+
+def test_one_handle_through_its_life_equals_fresh_handles_step_by_step():
+    """n = 5 (two quads, the second partly empty), ld = 8 and then 16, one handle through: commands; a schedule at ld 8; cleared; commands
+    and a schedule at ld 16 (the handle's buffer regrows); feedback for 5; wbc_gait_targets_measured over two runs of ticks; feedback
+    cleared; feedback for 3 and a run at n = 3; a terrain set and unset; destroy.  After every step its targets, masks, offsets and
+    state are bit for bit those of a fresh handle brought directly to that configuration, and what it refuses it refuses in the same
+    words: n above the schedule's, n above the feedback's, no feedback, measured targets with a terrain set."""
+    from quadruped_drake_amd import terrain as tr
+    n = 5
+    P, cmd, sc, times, dq, dv, gid = _inputs(16)
+    times, dq, dv = times[::5], dq[::5], dv[::5]                                             # 24 ticks over the 0.3 s
+    half = times.shape[0] // 2
+    cut = lambda a, ld: np.ascontiguousarray(a[..., :ld])
+
+    def fresh(ld, schedule, feedback=None):
+        f = RawFeedbackGait(TEN, P, n, None, ld, cut(cmd, ld), gid[:ld], sc[:ld], _schedule(ld) if schedule else None)
+        if feedback:
+            f.reset(tfc.PAR, feedback)
+        return f
+
+    def same(a, b):
+        return all(pe.same_bits(x, y) for x, y in zip(a, b))
+
+    def set_schedule(g, ld):
+        m, when, cmds, blend = _schedule(ld)
+        arrays = [_t(m), _t(when), _t(cmds)]
+        _lib.check(g.L.wbc_gait_set_schedule(g.h, g.stream, n, ld, float(blend), *[_ptr(a) for a in arrays]))
+
+    def refused(g, n_, what, measured=True):
+        """one call at n_ is refused with `what` in the message and writes nothing"""
+        tm, tq, tv = _t(cut(times[0], g.ld)), _t(cut(q[0], g.ld)), _t(cut(v[0], g.ld))
+        tg, mk, of = g.buffers(1)
+        if measured:
+            rc = g.L.wbc_gait_targets_measured(g.h, g.stream, n_, g.ld, _ptr(tm), _ptr(tq), _ptr(tv), _ptr(tg[0]), _ptr(mk[0]), _ptr(of[0]))
+        else:
+            rc = g.L.wbc_gait_targets(g.h, g.stream, n_, g.ld, _ptr(tm), _ptr(tg[0]), _ptr(mk[0]))
+        _sync()
+        return rc < 0 and what in g.L.wbc_last_error().decode() and (tg == FILL).all().item() and (mk == 0x55).all().item()
+
+    # 1. commands
+    g = fresh(8, False)
+    f = fresh(8, False)
+    plain8 = f.plain(n, cut(times, 8))
+    f.close()
+    assert same(g.plain(n, cut(times, 8)), plain8)
+    # 2. a schedule at ld 8
+    set_schedule(g, 8)
+    f = fresh(8, True)
+    sched8 = f.plain(n, cut(times, 8))
+    f.close()
+    assert same(g.plain(n, cut(times, 8)), sched8) and not same(sched8, plain8)
+    q, v = _measure(np.concatenate([sched8[0], sched8[0]], axis=2), dq, dv)                   # [ticks, 19 | 18, 16]: any finite trunk will do
+    assert refused(g, n + 1, "larger than the n of the handle's wbc_gait_set_schedule", measured=False)
+    # 3. cleared
+    _lib.check(g.L.wbc_gait_clear_schedule(g.h))
+    assert same(g.plain(n, cut(times, 8)), plain8) and same(g.plain(n + 1, cut(times, 8))[0][:, :, :n], plain8[0][:, :, :n])
+    # 4. commands and a schedule at ld 16: the buffer regrows
+    g.ld = 16
+    g.keep = [_t(cmd), _t(gid), _t(sc)]
+    _lib.check(g.L.wbc_gait_set_commands(g.h, _ptr(g.keep[0]), _ptr(g.keep[1]), _ptr(g.keep[2]), None))
+    set_schedule(g, 16)
+    f = fresh(16, True, feedback=n)
+    sched16 = f.plain(n, times)
+    assert same(g.plain(n, times), sched16) and pe.same_bits(sched16[0][:, :, :n], sched8[0][:, :, :n])
+    # 5. feedback for n = 5: wbc_gait_targets is what it was
+    g.reset(tfc.PAR, n)
+    assert same(g.plain(n, times), sched16)
+    # 6. measured targets over two runs of ticks: the state carries over
+    moved = []
+    for lo, hi in ((0, half), (half, 2 * half)):
+        got, want = g.measured(n, times[lo:hi], q[lo:hi], v[lo:hi]), f.measured(n, times[lo:hi], q[lo:hi], v[lo:hi])
+        assert same(got, want) and same(g.state(n), f.state(n))
+        moved.append(got[0])
+    f.close()
+    assert not pe.same_bits(np.concatenate(moved), sched16[0][:2 * half])                   # the pass did move footholds
+    assert refused(g, n + 1, "larger than the n of the handle's wbc_gait_set_feedback")
+    assert refused(g, n + 1, "larger than the n of the handle's wbc_gait_set_schedule", measured=False)
+    # 7. feedback cleared
+    _lib.check(g.L.wbc_gait_clear_feedback(g.h))
+    assert refused(g, n, "wbc_gait_set_feedback has not been called") and same(g.plain(n, times), sched16)
+    # 8. feedback for n = 3, a run at n = 3
+    g.reset(tfc.PAR, 3)
+    f = fresh(16, True, feedback=3)
+    assert same(g.measured(3, times[:half], q[:half], v[:half]), f.measured(3, times[:half], q[:half], v[:half])) and same(g.state(3), f.state(3))
+    assert refused(g, 4, "larger than the n of the handle's wbc_gait_set_feedback")
+    # 9. a terrain set and unset
+    tp, arr = gait.c_terrain_params(), tr.c_array([tr.slope(0.1, start=-1.0)])             # a slope under every foot: other rows
+    for h in (g, f):
+        _lib.check(h.L.wbc_gait_set_terrain(h.h, C.byref(tp), C.cast(arr, C.c_void_p), 1, None, None))
+    on = g.plain(n, times)
+    assert same(on, f.plain(n, times)) and not same(on, sched16) and refused(g, 3, "the handle has a terrain set")
+    for h in (g, f):
+        _lib.check(h.L.wbc_gait_set_terrain(h.h, None, None, 0, None, None))
+    assert same(g.plain(n, times), sched16)
+    assert same(g.measured(3, times[half:], q[half:], v[half:]), f.measured(3, times[half:], q[half:], v[half:])) and same(g.state(3), f.state(3))
+    f.close()
+    # 10. destroy
+    assert g.L.wbc_gait_destroy(g.h) == 0
 
 
 DAMAGE = [("q4", np.nan), ("q5", np.inf), ("v3", -np.inf), ("v4", np.nan), ("time", np.nan), ("time", np.inf), ("gait_id", 200), ("cmd", np.nan)]

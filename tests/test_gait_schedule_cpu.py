@@ -1,4 +1,4 @@
-"""The gait planner's command schedules (include_gait_schedule/wbc_gait_schedule.h), no GPU: the host instantiation of the SCHEDULE
+"""The gait planner's command schedules (include/wbc_gait_schedule.h), no GPU: the host instantiation of the SCHEDULE
 law of csrc/wbc_gait.hpp (tests/host_gait_schedule.py) against the numpy restatement of the header (tests/gait_schedule_oracle.py) on
 the plane and on a terrain, the exact relations with the plain law, continuity across a switch and a blend's ends, the argument
 checks that return before any device is touched, the binding table against the header, the twin under the sanitizers as a
@@ -22,7 +22,6 @@ import host_gait as hg
 import host_gait_schedule as hgs
 import host_gait_terrain as hgt
 import plant_edges as pe
-import test_abi_cpu as abi
 import test_gait_cpu as tgc
 import test_gait_terrain_cpu as tgt
 from quadruped_drake_amd import gait, terrain as tr
@@ -284,44 +283,12 @@ def test_abi_gait_schedule_misuse_without_device():
         g.set_schedule([1.0], [(0, 0, 0)])
 
 
-SCHEDULE_NAMES = ["wbc_gait_clear_schedule", "wbc_gait_schedule_kernel_info", "wbc_gait_set_schedule"]
-
-
-def test_schedule_prototype_table_equals_its_header(tmp_path):
-    """_lib.PROTOTYPES_SCHEDULE against include_gait_schedule/wbc_gait_schedule.h with the checker of tests/test_abi_cpu.py; the library
-    exports the three names and lib() bound them as the table says; the header stands alone as C99 with its two include directories."""
-    from quadruped_drake_amd import _lib
-    assert os.listdir(os.path.join(ROOT, "include_gait_schedule")) == ["wbc_gait_schedule.h"]
-    header = abi._header_prototypes(os.path.join("..", "include_gait_schedule", "*.h"))
-    assert sorted(header) == SCHEDULE_NAMES == sorted(_lib.PROTOTYPES_SCHEDULE)
-    assert header["wbc_gait_set_schedule"] == ("int", ["wbc_gait", "void*", "int", "int", "double", "uint8_t*", "double*", "double*"])
-    assert abi._prototype_mismatches(header, _lib.PROTOTYPES_SCHEDULE, _lib) == []
-    assert not set(_lib.PROTOTYPES_SCHEDULE) & set(_lib.PROTOTYPES)
-    t = dict(_lib.PROTOTYPES_SCHEDULE)
-    res, args = t["wbc_gait_set_schedule"]
-    t["wbc_gait_set_schedule"] = (res, args[:4] + args[5:])                                    # the blend dropped
-    bad = abi._prototype_mismatches(header, t, _lib)
-    assert len(bad) == 1 and bad[0].startswith("wbc_gait_set_schedule: 8 arguments in the header, 7"), bad
-    t["wbc_gait_set_schedule"] = (res, args[:3] + [args[4], args[3]] + args[5:])               # ld and blend swapped
-    bad = abi._prototype_mismatches(header, t, _lib)
-    assert len(bad) == 2 and all(b.startswith("wbc_gait_set_schedule: argument") for b in bad), bad
-    l = _lib.lib()
-    for s in SCHEDULE_NAMES:
-        fn = getattr(l, s)
-        assert fn.restype is _lib.PROTOTYPES_SCHEDULE[s][0] and list(fn.argtypes) == _lib.PROTOTYPES_SCHEDULE[s][1], s
-    src = tmp_path / "alone.c"
-    src.write_text('#include "wbc_gait_schedule.h"\nint main(void) { return WBC_GAIT_MAX_SWITCHES - 7; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-I",
-                    os.path.join(ROOT, "include_gait_schedule"), "-o", str(tmp_path / "alone"), str(src)], check=True, capture_output=True)
-    assert subprocess.run([str(tmp_path / "alone")]).returncode == 0 and gait.MAX_SWITCHES == 7
-
-
 def test_the_twin_runs_clean_under_the_sanitizers_as_a_stand_alone_program(tmp_path):
     """tools/host_gait_schedule_check.cpp + tools/host_gait.cpp built with -fsanitize=address,undefined (no recovery) and run: every m,
     an invalid schedule, both blends, the plane and a terrain, arrays exactly as long as the batch."""
     exe = tmp_path / "check"
     subprocess.run(["g++", "-O1", "-g", "-std=c++20", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "include_gait_schedule"), "-o", str(exe),
+                    "-I", os.path.join(ROOT, "include"), "-o", str(exe),
                     os.path.join(ROOT, "tools", "host_gait_schedule_check.cpp"), os.path.join(ROOT, "tools", "host_gait.cpp")],
                    check=True, capture_output=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True)

@@ -1,4 +1,4 @@
-"""The gait planner's command schedules on the MI355X (include_gait_schedule/wbc_gait_schedule.h; gait.GaitPlanner.set_schedule):
+"""The gait planner's command schedules on the MI355X (include/wbc_gait_schedule.h; gait.GaitPlanner.set_schedule):
 wbc_gait_schedule_targets_kernel and wbc_gait_schedule_terrain_targets_kernel against the host instantiation of the same law
 (tests/host_gait_schedule.py) at the bars of tests/test_gait_schedule_cpu.py, their resources, the plain kernels' bits behind m = 0
 and behind a cleared schedule, invalid schedules in every robot slot of a wavefront, a scheduled gait as the target source of

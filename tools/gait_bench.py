@@ -9,9 +9,9 @@
     3 s) and of the target-lookup kernel beside it: HIP events around bursts of back-to-back launches after a warm-up, the median
     over the bursts.  A library with the gait's terrain also gets wbc_gait_terrain_targets_kernel timed in the same process: the same
     planner on sixteen kerbs and stairs, each instance with its own profile and scale, FIT.  A library with the command schedules
-    (include_gait_schedule/wbc_gait_schedule.h) also gets wbc_gait_schedule_targets_kernel and wbc_gait_schedule_terrain_targets_kernel
+    (include/wbc_gait_schedule.h) also gets wbc_gait_schedule_targets_kernel and wbc_gait_schedule_terrain_targets_kernel
     timed: the same planner, every instance with its own three switches inside the 3 s of sampled times, blend 0.5 -- and the plain
-    kernels again once the schedule is cleared.  A library with the foot-placement feedback (include_gait_feedback/wbc_gait_feedback.h)
+    kernels again once the schedule is cleared.  A library with the foot-placement feedback (include/wbc_gait_feedback.h)
     gets wbc_gait_targets_measured timed, which is the plain kernel and wbc_gait_feedback_kernel after it: two launches; the pass's
     own time is that pair's less the plain kernel's.
   loop: time per 1 ms tick of wbc_ground_rollout at 16 substeps, MPTC, with the targets looked up in a recorded trot

@@ -9,6 +9,88 @@
 
 using namespace wbc;
 
+namespace {
+
+struct Terrain {    // wbc_gait_set_terrain's arguments
+  const wbc_gait_terrain_params* params;
+  const wbc_terrain_profile* profiles;
+  int count;
+  const uint8_t* id;
+  const double* scale;
+};
+struct Schedule {   // wbc_gait_set_schedule's arguments; knots (optional): where the resolved schedules go
+  double blend;
+  const uint8_t* nswitch;
+  const double* when;
+  const double* cmds;
+  double* knots;
+};
+
+// Instance i's 54 rows and its mask from the <TERRAIN, SCHEDULE> instantiation of the law: the four feet one after the other, then
+// the body.  G, S: the instance's ground and schedule where the instantiation has them.  diag: host_gait_batch's.
+template <bool TERRAIN, bool SCHEDULE>
+void instance(const double* table, int count, const double* ter, const GaitIn& in, const GaitGround* G, const GaitSchedule* S, size_t ld,
+              size_t i, double* targets, uint8_t* contact_mask, double* diag, int diag_foot) {
+  GaitClock c = gait_clock(table, count, in);
+  if constexpr (TERRAIN || SCHEDULE) gait_clock_spoil(c, (TERRAIN && G->bad) | (SCHEDULE && S->bad));
+  double b[18], f[9], gr[12], run[2], seen[2] = {0.0, 0.0};
+  for (int l = 0; l < 4; l++) {
+    gait_foot<TERRAIN, SCHEDULE>(table, in, c, l, f, run, ter, G, gr + 3 * l, S);
+    if (l == diag_foot) { seen[0] = run[0]; seen[1] = run[1]; }
+    for (int k = 0; k < 9; k++) targets[(size_t)(18 + 9 * l + k) * ld + i] = f[k];
+  }
+  gait_body<TERRAIN, SCHEDULE>(table, in, c, b, ter, gr, S);
+  for (int k = 0; k < 18; k++) targets[(size_t)k * ld + i] = b[k];
+  contact_mask[i] = (uint8_t)c.mask;
+  if (diag) {
+    diag[i] = c.k;
+    diag[ld + i] = (double)c.phase;
+    diag[2 * ld + i] = seen[1];
+    diag[3 * ld + i] = seen[0];
+  }
+}
+
+// What the three entry points below share: the arguments checked in the order of their return codes, the tables packed, and every
+// instance through the instantiation its handle would launch.  T, sch: null for a handle without a terrain, without a schedule.
+int batch(const wbc_gait_params* params, const wbc_gait_stride* strides, int count, const Terrain* T, const Schedule* sch, int n, int ld,
+          const double* time, const double* cmd, const uint8_t* gait_id, const double* stride_scale, const double* start, double* targets,
+          uint8_t* contact_mask, double* table_out = nullptr, double* diag = nullptr, int diag_foot = -1) {
+  if (gait_error(params, strides, count)) return -1;
+  if (sch && (!sch->nswitch || !sch->when || !sch->cmds || !(sch->blend >= 0.0) || not_finite(sch->blend))) return -5;
+  double table[GAIT_TABLE_DOUBLES] = {0.0}, ter[GAIT_TERRAIN_DOUBLES] = {0.0};
+  gait_pack(params, strides, count, table);
+  if (T) {
+    if (gait_terrain_error(T->params)) return -2;
+    if (!T->profiles || T->count < 1 || T->count > TERRAIN_MAX_PROFILES) return -3;
+    for (int p = 0; p < T->count; p++) {
+      const wbc_terrain_profile& f = T->profiles[p];
+      if (terrain_profile_error(f.nk, f.x0, f.y0, f.yaw, f.s, f.h)) return -3;
+    }
+    if (gait_terrain_fit_error(T->params, table)) return -4;
+    gait_terrain_pack(T->params, table, T->profiles, T->count, ter);
+  }
+  if (table_out)
+    for (int k = 0; k < GAIT_TABLE_DOUBLES; k++) table_out[k] = table[k];
+  double own[GAIT_SCHEDULE_ROWS];
+  for (int i = 0; i < n; i++) {
+    const GaitIn in = gait_load(time, cmd, gait_id, stride_scale, start, (size_t)ld, (size_t)i);
+    GaitGround G{};
+    GaitSchedule S{};
+    if (T) G = gait_ground(ter, T->count, T->id ? (int)T->id[i] : 0, T->scale ? T->scale[i] : 1.0);
+    if (sch) {
+      double* k = sch->knots ? sch->knots + i : own;
+      const size_t ldk = sch->knots ? (size_t)ld : 1;
+      gait_schedule_resolve(in, sch->blend, (int)sch->nswitch[i], sch->when + i, sch->cmds + i, (size_t)ld, k, ldk);
+      S = gait_schedule_load(k, ldk, 0, sch->blend);
+    }
+    const auto rows = T ? (sch ? instance<true, true> : instance<true, false>) : (sch ? instance<false, true> : instance<false, false>);
+    rows(table, count, ter, in, &G, &S, (size_t)ld, (size_t)i, targets, contact_mask, diag, diag_foot);
+  }
+  return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 // wbc_gait_create + wbc_gait_set_commands + wbc_gait_targets with host pointers.  Returns 0, -1 on arguments wbc_gait_check refuses.
@@ -17,31 +99,8 @@ extern "C" {
 int host_gait_batch(const wbc_gait_params* params, const wbc_gait_stride* strides, int count, int n, int ld, const double* time,
                     const double* cmd, const uint8_t* gait_id, const double* stride_scale, const double* start, double* targets,
                     uint8_t* contact_mask, double* table_out, double* diag, int diag_foot) {
-  if (gait_error(params, strides, count)) return -1;
-  double table[GAIT_TABLE_DOUBLES] = {0.0};
-  gait_pack(params, strides, count, table);
-  if (table_out)
-    for (int k = 0; k < GAIT_TABLE_DOUBLES; k++) table_out[k] = table[k];
-  for (int i = 0; i < n; i++) {
-    const GaitIn in = gait_load(time, cmd, gait_id, stride_scale, start, (size_t)ld, (size_t)i);
-    const GaitClock c = gait_clock(table, count, in);
-    double b[18], f[9], run[2], seen[2] = {0.0, 0.0};
-    gait_body(table, in, c, b);
-    for (int k = 0; k < 18; k++) targets[(size_t)k * ld + i] = b[k];
-    for (int l = 0; l < 4; l++) {
-      gait_foot(table, in, c, l, f, run);
-      if (l == diag_foot) { seen[0] = run[0]; seen[1] = run[1]; }
-      for (int k = 0; k < 9; k++) targets[(size_t)(18 + 9 * l + k) * ld + i] = f[k];
-    }
-    contact_mask[i] = (uint8_t)c.mask;
-    if (diag) {
-      diag[i] = c.k;
-      diag[ld + i] = (double)c.phase;
-      diag[2 * (size_t)ld + i] = seen[1];
-      diag[3 * (size_t)ld + i] = seen[0];
-    }
-  }
-  return 0;
+  return batch(params, strides, count, nullptr, nullptr, n, ld, time, cmd, gait_id, stride_scale, start, targets, contact_mask, table_out, diag,
+               diag_foot);
 }
 
 // The same with a terrain (include/wbc_gait_terrain.h): + wbc_gait_set_terrain with host pointers.  Returns -2 on what
@@ -50,33 +109,11 @@ int host_gait_terrain_batch(const wbc_gait_params* params, const wbc_gait_stride
                             const wbc_terrain_profile* profiles, int tcount, int n, int ld, const double* time, const double* cmd,
                             const uint8_t* gait_id, const double* stride_scale, const double* start, const uint8_t* terrain_id,
                             const double* terrain_scale, double* targets, uint8_t* contact_mask) {
-  if (gait_error(params, strides, count)) return -1;
-  if (gait_terrain_error(tparams)) return -2;
-  if (!profiles || tcount < 1 || tcount > TERRAIN_MAX_PROFILES) return -3;
-  for (int p = 0; p < tcount; p++)
-    if (terrain_profile_error(profiles[p].nk, profiles[p].x0, profiles[p].y0, profiles[p].yaw, profiles[p].s, profiles[p].h)) return -3;
-  double table[GAIT_TABLE_DOUBLES] = {0.0}, ter[GAIT_TERRAIN_DOUBLES] = {0.0};
-  gait_pack(params, strides, count, table);
-  if (gait_terrain_fit_error(tparams, table)) return -4;
-  gait_terrain_pack(tparams, table, profiles, tcount, ter);
-  for (int i = 0; i < n; i++) {
-    const GaitIn in = gait_load(time, cmd, gait_id, stride_scale, start, (size_t)ld, (size_t)i);
-    const GaitGround G = gait_ground(ter, tcount, terrain_id ? (int)terrain_id[i] : 0, terrain_scale ? terrain_scale[i] : 1.0);
-    GaitClock c = gait_clock(table, count, in);
-    gait_clock_spoil(c, G.bad);
-    double b[18], f[9], gr[12];
-    for (int l = 0; l < 4; l++) {
-      gait_foot<true>(table, in, c, l, f, nullptr, ter, &G, gr + 3 * l);
-      for (int k = 0; k < 9; k++) targets[(size_t)(18 + 9 * l + k) * ld + i] = f[k];
-    }
-    gait_body<true>(table, in, c, b, ter, gr);
-    for (int k = 0; k < 18; k++) targets[(size_t)k * ld + i] = b[k];
-    contact_mask[i] = (uint8_t)c.mask;
-  }
-  return 0;
+  const Terrain T{tparams, profiles, tcount, terrain_id, terrain_scale};
+  return batch(params, strides, count, &T, nullptr, n, ld, time, cmd, gait_id, stride_scale, start, targets, contact_mask);
 }
 
-// The same under command schedules (include_gait_schedule/wbc_gait_schedule.h): + wbc_gait_set_schedule with host pointers, on the plane
+// The same under command schedules (include/wbc_gait_schedule.h): + wbc_gait_set_schedule with host pointers, on the plane
 // (tparams NULL) or on a terrain.  Returns -5 on null schedule arrays or a blend that is negative or not finite.  knots (optional,
 // [GAIT_SCHEDULE_ROWS][ld]): the resolved schedules, as the handle's buffer holds them.
 int host_gait_schedule_batch(const wbc_gait_params* params, const wbc_gait_stride* strides, int count, const wbc_gait_terrain_params* tparams,
@@ -84,47 +121,9 @@ int host_gait_schedule_batch(const wbc_gait_params* params, const wbc_gait_strid
                              const uint8_t* gait_id, const double* stride_scale, const double* start, const uint8_t* terrain_id,
                              const double* terrain_scale, double blend, const uint8_t* nswitch, const double* when, const double* cmds,
                              double* targets, uint8_t* contact_mask, double* knots) {
-  if (gait_error(params, strides, count)) return -1;
-  if (!nswitch || !when || !cmds || !(blend >= 0.0) || not_finite(blend)) return -5;
-  double table[GAIT_TABLE_DOUBLES] = {0.0}, ter[GAIT_TERRAIN_DOUBLES] = {0.0};
-  gait_pack(params, strides, count, table);
-  if (tparams) {
-    if (gait_terrain_error(tparams)) return -2;
-    if (!profiles || tcount < 1 || tcount > TERRAIN_MAX_PROFILES) return -3;
-    for (int p = 0; p < tcount; p++)
-      if (terrain_profile_error(profiles[p].nk, profiles[p].x0, profiles[p].y0, profiles[p].yaw, profiles[p].s, profiles[p].h)) return -3;
-    if (gait_terrain_fit_error(tparams, table)) return -4;
-    gait_terrain_pack(tparams, table, profiles, tcount, ter);
-  }
-  double own[GAIT_SCHEDULE_ROWS];
-  for (int i = 0; i < n; i++) {
-    const GaitIn in = gait_load(time, cmd, gait_id, stride_scale, start, (size_t)ld, (size_t)i);
-    double* k = knots ? knots + i : own;
-    const size_t ldk = knots ? (size_t)ld : 1;
-    gait_schedule_resolve(in, blend, (int)nswitch[i], when + i, cmds + i, (size_t)ld, k, ldk);
-    const GaitSchedule S = gait_schedule_load(k, ldk, 0, blend);
-    GaitClock c = gait_clock(table, count, in);
-    double b[18], f[9], gr[12];
-    if (tparams) {
-      const GaitGround G = gait_ground(ter, tcount, terrain_id ? (int)terrain_id[i] : 0, terrain_scale ? terrain_scale[i] : 1.0);
-      gait_clock_spoil(c, G.bad | S.bad);
-      for (int l = 0; l < 4; l++) {
-        gait_foot<true, true>(table, in, c, l, f, nullptr, ter, &G, gr + 3 * l, &S);
-        for (int r = 0; r < 9; r++) targets[(size_t)(18 + 9 * l + r) * ld + i] = f[r];
-      }
-      gait_body<true, true>(table, in, c, b, ter, gr, &S);
-    } else {
-      gait_clock_spoil(c, S.bad);
-      for (int l = 0; l < 4; l++) {
-        gait_foot<false, true>(table, in, c, l, f, nullptr, nullptr, nullptr, nullptr, &S);
-        for (int r = 0; r < 9; r++) targets[(size_t)(18 + 9 * l + r) * ld + i] = f[r];
-      }
-      gait_body<false, true>(table, in, c, b, nullptr, nullptr, &S);
-    }
-    for (int r = 0; r < 18; r++) targets[(size_t)r * ld + i] = b[r];
-    contact_mask[i] = (uint8_t)c.mask;
-  }
-  return 0;
+  const Terrain T{tparams, profiles, tcount, terrain_id, terrain_scale};
+  const Schedule sch{blend, nswitch, when, cmds, knots};
+  return batch(params, strides, count, tparams ? &T : nullptr, &sch, n, ld, time, cmd, gait_id, stride_scale, start, targets, contact_mask);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // host_gait_feedback_check.cpp -- TEST TOOL, not product code.
 // A stand-alone program over tools/host_gait_feedback.cpp and tools/host_gait.cpp: the host instantiation of the gait planner's
-// foot-placement feedback (include_gait_feedback/wbc_gait_feedback.h) driven tick by tick through the cases of
+// foot-placement feedback (include/wbc_gait_feedback.h) driven tick by tick through the cases of
 // tests/test_gait_feedback_cpu.py -- a perturbed walk on two strides, zero gains, a measurement on the plan, a constant velocity error,
 // and damaged instances -- on arrays exactly as long as the batch.  That test builds it with -fsanitize=address,undefined and runs it:
 // the program prints a checksum and returns 0, and the sanitizers abort it on anything they find.
@@ -10,7 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "wbc_gait_feedback.h"
+#include "../include/wbc_gait_feedback.h"
 
 extern "C" int host_gait_batch(const wbc_gait_params* params, const wbc_gait_stride* strides, int count, int n, int ld, const double* time,
                                const double* cmd, const uint8_t* gait_id, const double* stride_scale, const double* start, double* targets,

@@ -1,6 +1,6 @@
 // host_gait_schedule_check.cpp -- TEST TOOL, not product code.
 // A stand-alone program over tools/host_gait.cpp: the host instantiation of the gait planner's law under command schedules
-// (include_gait_schedule/wbc_gait_schedule.h) on a batch that visits every m = 0 .. 7, an invalid m, blends of 0 and 0.5, the plane
+// (include/wbc_gait_schedule.h) on a batch that visits every m = 0 .. 7, an invalid m, blends of 0 and 0.5, the plane
 // and a terrain.  tests/test_gait_schedule_cpu.py builds it with -fsanitize=address,undefined and runs it: the program prints a
 // checksum and returns 0, and the sanitizers abort it on anything they find.
 #include <math.h>
@@ -9,8 +9,8 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "wbc_gait_schedule.h"
-#include "wbc_gait_terrain.h"
+#include "../include/wbc_gait_schedule.h"
+#include "../include/wbc_gait_terrain.h"
 
 extern "C" int host_gait_schedule_batch(const wbc_gait_params* params, const wbc_gait_stride* strides, int count, const wbc_gait_terrain_params* tparams,
                                         const wbc_terrain_profile* profiles, int tcount, int n, int ld, const double* time, const double* cmd,
