@@ -181,7 +181,9 @@ int wbc_stats_reduce(const double* gathered, int world, wbc_stats* out);
 
 /* Closed-loop rollouts.  If set (device pointer, [18][ld], same ld as wbc_step),
  * every wbc_step also writes the generalized accelerations vd of its QP solution (rows in the
- * order of v: w_WB-dot, v_WBo-dot, 12 joint accelerations in the caller's joint order).  NULL disables. */
+ * order of v: w_WB-dot, v_WBo-dot, 12 joint accelerations in the caller's joint order).  NULL disables.
+ * Binding selects another kernel of the same law (one that also forms these rows; wbc_kernel_info follows):
+ * torques, metrics and status are the same bits either way. */
 int wbc_set_vdot_output(wbc_handle h, double* vdot);
 
 /* Semi-implicit Euler on the reference's state conventions, in place on device arrays:
@@ -218,8 +220,8 @@ int wbc_set_variant(wbc_handle h, int variant);
 /* The variant a wbc_step of n instances would run (always 3). */
 int wbc_variant_for(wbc_handle h, int n);
 
-/* Kernel resource report for the variant of the most recent launch (or of max_batch before any):
- * registers, scratch bytes/lane, LDS bytes. */
+/* Kernel resource report for the tick kernel a wbc_step on this handle would launch NOW (its law, its
+ * torque box, and whether wbc_set_vdot_output has a buffer bound): registers, scratch bytes/lane, LDS bytes. */
 int wbc_kernel_info(wbc_handle h, int* num_vgpr, int* scratch_bytes, int* lds_bytes, int* block_threads);
 /* The same for the persistent closed-loop kernel wbc_rollout launches for this handle (its own register allocation: the tick
  * inlined into the step loop). */

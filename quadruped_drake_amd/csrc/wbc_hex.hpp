@@ -861,7 +861,9 @@ WBC_HD double pick3(int sb, double a, double b, double c) { return (sb == 0) ? a
 
 // The tick.  Every lane of the row calls this with its own Q (lane id h = 4*leg + sub).
 // out_tau(row, x): lane (leg, j<3) writes the torque of joint 3*leg+j;  out_met: see the kernel.
-template <class Q, int KIND, bool TB, bool WARM = false, class Park, class In, class OutTau, class OutMet>
+// VD = false (the tick kernels of a handle with no acceleration buffer bound, wbc_set_vdot_output): rows 4..21 of out_met are not formed -- the
+// parks of Ji's column, rf and bc, their reads, the cross product and the dot are not compiled; torques, metrics and status are the same expressions.
+template <class Q, int KIND, bool TB, bool WARM = false, bool VD = true, class Park, class In, class OutTau, class OutMet>
 WBC_HD int hex_tick(const ModelC& m, const ParamsX& P, Q& qo, In in, unsigned mask, double mu, double mass_scale,
                     Park& pk, OutTau out_tau, OutMet out_met, int* iters_out, bool* seed = nullptr) {
   const int h = qo.lane();
@@ -1448,9 +1450,11 @@ WBC_HD int hex_tick(const ModelC& m, const ParamsX& P, Q& qo, In in, unsigned ma
     for (int k = 0; k < 6; k++) { pk.lput(LP_YROW + k, Yrow[k]); pk.lput(LP_BCOL + k, bcol[k]); pk.lput(LP_AB0 + k, ab0[k]); }
     for (int k = 0; k < 3; k++) {
       pk.lput(LP_DROW + k, Drow[k]);
-      pk.lput(LP_JIC + k, pick3(sb, Ji[k], Ji[3 + k], Ji[6 + k]));
-      pk.lput(LP_RF + k, rf[k]);
-      pk.lput(LP_BC + k, bc[k]);
+      if constexpr (VD) {   // read again by the acceleration rows only
+        pk.lput(LP_JIC + k, pick3(sb, Ji[k], Ji[3 + k], Ji[6 + k]));
+        pk.lput(LP_RF + k, rf[k]);
+        pk.lput(LP_BC + k, bc[k]);
+      }
     }
     pk.lput(LP_T0, t0_own);
     pk.lput(LP_MET + 0, vrow_own); pk.lput(LP_MET + 1, vconst); pk.lput(LP_MET + 2, met_V);
@@ -1501,8 +1505,10 @@ WBC_HD int hex_tick(const ModelC& m, const ParamsX& P, Q& qo, In in, unsigned ma
       // integrates them, so they must be defined); a malformed instance has no position error to report either
       if (colv) out_tau(m.act_inv[3 * l + sb], 0.0);
       out_met(0, 0.0); out_met(1, 0.0); out_met(2, 0.0); out_met(3, 0.0);
-      for (int i = 0; i < 6; i++) out_met(4 + i, 0.0);
-      if (colv) out_met(4 + 6 + m.q_perm[3 * l + sb], 0.0);
+      if constexpr (VD) {
+        for (int i = 0; i < 6; i++) out_met(4 + i, 0.0);
+        if (colv) out_met(4 + 6 + m.q_perm[3 * l + sb], 0.0);
+      }
       *iters_out = 0;
       return ST_SINGULAR;
     }
@@ -1563,12 +1569,16 @@ WBC_HD int hex_tick(const ModelC& m, const ParamsX& P, Q& qo, In in, unsigned ma
   double jic[3];
   {
     for (int k = 0; k < 6; k++) { Yrow[k] = pk.lget(LP_YROW + k); bcol[k] = pk.lget(LP_BCOL + k); ab0[k] = pk.lget(LP_AB0 + k); }
-    for (int k = 0; k < 3; k++) { Drow[k] = pk.lget(LP_DROW + k); jic[k] = pk.lget(LP_JIC + k); rf[k] = pk.lget(LP_RF + k); }
+    for (int k = 0; k < 3; k++) {
+      Drow[k] = pk.lget(LP_DROW + k);
+      if constexpr (VD) { jic[k] = pk.lget(LP_JIC + k); rf[k] = pk.lget(LP_RF + k); }
+    }
     t0_own = pk.lget(LP_T0);
     vrow_own = pk.lget(LP_MET + 0); vconst = pk.lget(LP_MET + 1); met_V = pk.lget(LP_MET + 2);
     met_Vdot = pk.lget(LP_MET + 3); met_err = pk.lget(LP_MET + 4);
   }
-  const double bcp[3] = {pk.lget(LP_BC + 0), pk.lget(LP_BC + 1), pk.lget(LP_BC + 2)};
+  double bcp[3];
+  if constexpr (VD) { bcp[0] = pk.lget(LP_BC + 0); bcp[1] = pk.lget(LP_BC + 1); bcp[2] = pk.lget(LP_BC + 2); }
   const double z0 = qo.leg_bcast(z, 0), z1 = qo.leg_bcast(z, 1), z2 = qo.leg_bcast(z, 2);
   {
     double ab[6];
@@ -1583,14 +1593,16 @@ WBC_HD int hex_tick(const ModelC& m, const ParamsX& P, Q& qo, In in, unsigned ma
     if (qo.any16(bad)) status = ST_SINGULAR;
     if (colv) out_tau(m.act_inv[3 * l + sb], (status == ST_SINGULAR) ? 0.0 : s);
     // generalized accelerations of the QP solution (rows 4..21 of out_met); zeros with the zero torques of status 2
-    const bool sing = (status == ST_SINGULAR);
-    for (int i = 0; i < 6; i++) out_met(4 + i, sing ? 0.0 : ab[i]);
-    double t[3], y[3];
-    cross(ab, rf, t);
-    const double zl[3] = {z0, z1, z2};
-    for (int i = 0; i < 3; i++) y[i] = (ct ? bcp[i] : zl[i]) - (ab[3 + i] + t[i]);
-    const double qdd = jic[0] * y[0] + jic[1] * y[1] + jic[2] * y[2];
-    if (colv) out_met(4 + 6 + m.q_perm[3 * l + sb], sing ? 0.0 : qdd);
+    if constexpr (VD) {
+      const bool sing = (status == ST_SINGULAR);
+      for (int i = 0; i < 6; i++) out_met(4 + i, sing ? 0.0 : ab[i]);
+      double t[3], y[3];
+      cross(ab, rf, t);
+      const double zl[3] = {z0, z1, z2};
+      for (int i = 0; i < 3; i++) y[i] = (ct ? bcp[i] : zl[i]) - (ab[3 + i] + t[i]);
+      const double qdd = jic[0] * y[0] + jic[1] * y[1] + jic[2] * y[2];
+      if (colv) out_met(4 + 6 + m.q_perm[3 * l + sb], sing ? 0.0 : qdd);
+    }
   }
   const bool sing = (status == ST_SINGULAR);
   const double errm = sing ? 0.0 : met_err;

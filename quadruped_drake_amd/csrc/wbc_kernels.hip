@@ -312,13 +312,20 @@ __device__ __forceinline__ int hex_effective_block(int b, int nblocks) {
 }
 
 // One wavefront per SIMD by design: 446 registers (two per SIMD by amdgpu_waves_per_eu(2): 996 B/lane of scratch, 2.3x slower, profiles/r02)
-template <int KIND, bool TB = false>
+// wbc_hex_kernel<KIND, TB>: the tick of a handle with no acceleration buffer bound (launch() picks by d_vdot); it never reads `vdot` and forms none of
+// the rows (hex_tick<..., VD = false>).  wbc_hex_kernel<KIND, TB, VdotRows>: the same tick with rows 4..21.  A tag in a trailing pack instead of a
+// third bool, so that the kernel every torque-only caller launches -- the headline's -- prints under the name the tick kernel of a law has always had
+// in a profiler's listing (bench.py's roofline.kernel and its look-up in profiles/r06/kernel_stats.csv, tools/).
+struct VdotRows {};
+template <int KIND, bool TB = false, class... ROWS>
 __global__ void __launch_bounds__(HEX_BLOCK) __attribute__((amdgpu_waves_per_eu(1)))
 wbc_hex_kernel(const wbc::ModelC* __restrict__ mp, const wbc::ParamsX* __restrict__ pp, int n, int ld,
                const double* __restrict__ q, const double* __restrict__ v, const double* __restrict__ tg,
                const uint8_t* __restrict__ mask, const double* __restrict__ mu,
                const double* __restrict__ ms, double* __restrict__ tau, double* __restrict__ met,
                int32_t* __restrict__ status, StatsDev* __restrict__ stats, double* __restrict__ vdot) {
+  static_assert(sizeof...(ROWS) <= 1, "wbc_hex_kernel<KIND, TB> or wbc_hex_kernel<KIND, TB, VdotRows>");
+  constexpr bool VD = sizeof...(ROWS) == 1;
   constexpr int PER_LANE = (NIN * HROBOTS + HEX_BLOCK - 1) / HEX_BLOCK;   // 6 input words per lane
   constexpr int MPER = (MODEL_PAD_WORDS + HEX_BLOCK - 1) / HEX_BLOCK;
   __shared__ double mbuf[MPER * HEX_BLOCK];
@@ -400,7 +407,9 @@ wbc_hex_kernel(const wbc::ModelC* __restrict__ mp, const wbc::ParamsX* __restric
   const bool lead = qo.h == 0;
   auto om = [&](int k, double x) {   // rows 0..3: metrics (lead lane), rows 4..9: base accelerations (lead), 10..21: own joint
     if (k >= 4) {
-      if (live && vdot && (k >= 10 || lead)) vdot[(size_t)(k - 4) * ld + ii] = x;
+      if constexpr (VD) {
+        if (live && vdot && (k >= 10 || lead)) vdot[(size_t)(k - 4) * ld + ii] = x;
+      }
       return;
     }
     if (live && lead && met) met[(size_t)k * ld + ii] = x;
@@ -414,7 +423,7 @@ wbc_hex_kernel(const wbc::ModelC* __restrict__ mp, const wbc::ParamsX* __restric
   for (int k = 0; k < WBC_FORCE_SCRATCH; k++) junk[k] = inbuf[k];
 #endif
   ParkLds park(parkbuf + slot * wbc::PK_N, lanebuf + threadIdx.x);
-  const int st = wbc::hex_tick<HexDev, KIND, TB>(m, P, qo, in, mk, mui, msi, park, ot, om, &iters);
+  const int st = wbc::hex_tick<HexDev, KIND, TB, false, VD>(m, P, qo, in, mk, mui, msi, park, ot, om, &iters);
 #ifdef WBC_FORCE_SCRATCH
   if (junk[threadIdx.x % WBC_FORCE_SCRATCH] == 1.2345e300) iters++;
 #endif
@@ -691,30 +700,41 @@ extern "C" void wbc_set_error_(const char* msg) { snprintf(g_err, sizeof g_err, 
 // The one place that says which kernel runs a handle's (law, torque box): launch(), wbc_rollout and the two *_kernel_info entry
 // points all go through tick_kernels(), so the registers kernel_info reports are those of the kernel that is launched.
 // torque box: a second constraint slot per lane, |tau_j| <= tau_max (wbc_hex.hpp).  A null entry is not part of this build.
+// tick: with the acceleration rows, for a handle that has a buffer bound (wbc_set_vdot_output); tick_novd: the same tick without them, for every
+// other handle.  tick_kernels() hands out the one of the two that the handle would launch NOW as `tick`.
 struct TickKernels {
-  decltype(&wbc_hex_kernel<wbc::KIND_ID, false>) tick;
+  decltype(&wbc_hex_kernel<wbc::KIND_ID, false, VdotRows>) tick;
   decltype(&wbc_hex_rollout_kernel<wbc::KIND_ID, false>) rollout;
+  decltype(&wbc_hex_kernel<wbc::KIND_ID, false, VdotRows>) tick_novd;
 };
 struct TickTable { TickKernels law[2][4]; };
 static_assert(WBC_KIND_ID == 0 && WBC_KIND_MPTC == 1 && WBC_KIND_PC == 2 && WBC_KIND_CLF == 3, "the table's second index is the ABI's kind");
 static const TickTable kTickKernels = [] {
   TickTable t{};
 #ifdef WBC_DEV_ONLY   // diagnostic builds (tools/build_cuts.sh): ONE law instantiated, seconds to compile
-  t.law[false][WBC_DEV_ONLY].tick = wbc_hex_kernel<WBC_DEV_ONLY, false>;
+  t.law[false][WBC_DEV_ONLY].tick = wbc_hex_kernel<WBC_DEV_ONLY, false, VdotRows>;
+  t.law[false][WBC_DEV_ONLY].tick_novd = wbc_hex_kernel<WBC_DEV_ONLY, false>;
 #else
   // The code object lays the kernels out in the order of their first mention, and placement alone moves the headline by up to 2 %
-  // (DESIGN.md section 8): the order stays what it has been -- ticks before rollouts, torque box before plain.
+  // (DESIGN.md section 8): the order stays what it has been -- ticks before rollouts, torque box before plain -- and the ticks without the
+  // acceleration rows come after all of them.
   auto ticks = [&t](auto tb) {
     constexpr bool TB = decltype(tb)::value;
-    t.law[TB][WBC_KIND_ID].tick = wbc_hex_kernel<wbc::KIND_ID, TB>;     t.law[TB][WBC_KIND_MPTC].tick = wbc_hex_kernel<wbc::KIND_MPTC, TB>;
-    t.law[TB][WBC_KIND_PC].tick = wbc_hex_kernel<wbc::KIND_PC, TB>;     t.law[TB][WBC_KIND_CLF].tick = wbc_hex_kernel<wbc::KIND_CLF, TB>;
+    t.law[TB][WBC_KIND_ID].tick = wbc_hex_kernel<wbc::KIND_ID, TB, VdotRows>;     t.law[TB][WBC_KIND_MPTC].tick = wbc_hex_kernel<wbc::KIND_MPTC, TB, VdotRows>;
+    t.law[TB][WBC_KIND_PC].tick = wbc_hex_kernel<wbc::KIND_PC, TB, VdotRows>;     t.law[TB][WBC_KIND_CLF].tick = wbc_hex_kernel<wbc::KIND_CLF, TB, VdotRows>;
   };
   auto rollouts = [&t](auto tb) {
     constexpr bool TB = decltype(tb)::value;
     t.law[TB][WBC_KIND_ID].rollout = wbc_hex_rollout_kernel<wbc::KIND_ID, TB>;   t.law[TB][WBC_KIND_MPTC].rollout = wbc_hex_rollout_kernel<wbc::KIND_MPTC, TB>;
     t.law[TB][WBC_KIND_PC].rollout = wbc_hex_rollout_kernel<wbc::KIND_PC, TB>;   t.law[TB][WBC_KIND_CLF].rollout = wbc_hex_rollout_kernel<wbc::KIND_CLF, TB>;
   };
+  auto ticks_novd = [&t](auto tb) {
+    constexpr bool TB = decltype(tb)::value;
+    t.law[TB][WBC_KIND_ID].tick_novd = wbc_hex_kernel<wbc::KIND_ID, TB>;   t.law[TB][WBC_KIND_MPTC].tick_novd = wbc_hex_kernel<wbc::KIND_MPTC, TB>;
+    t.law[TB][WBC_KIND_PC].tick_novd = wbc_hex_kernel<wbc::KIND_PC, TB>;   t.law[TB][WBC_KIND_CLF].tick_novd = wbc_hex_kernel<wbc::KIND_CLF, TB>;
+  };
   ticks(std::true_type{}); ticks(std::false_type{}); rollouts(std::true_type{}); rollouts(std::false_type{});
+  ticks_novd(std::true_type{}); ticks_novd(std::false_type{});
 #endif
   return t;
 }();
@@ -724,6 +744,7 @@ static int tick_kernels(const wbc_handle_s* h, const char* rollout_fn, TickKerne
   *out = kTickKernels.law[h->torque_box][h->kind];
   if (rollout_fn && !out->rollout) return misuse(rollout_fn, "not part of a WBC_DEV_ONLY diagnostic build");
   if (!out->tick) return misuse("this diagnostic build carries one law only (WBC_DEV_ONLY)");
+  if (!h->d_vdot) out->tick = out->tick_novd;   // nobody receives the accelerations: the tick that does not form them
   return 0;
 }
 

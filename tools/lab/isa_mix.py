@@ -57,7 +57,7 @@ def phases(kind, extra):
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-DWBC_STAMPS", "-DWBC_DEV_ONLY=" + kind, "-S", "--cuda-device-only", "-o", "/tmp/asm/mix.s",
                            os.path.join(ROOT, "quadruped_drake_amd", "csrc", "wbc_kernels.hip")] + extra, stderr=subprocess.DEVNULL)
     txt = open("/tmp/asm/mix.s").read().split("\n")
-    key = "wbc_hex_kernelILi%sELb0E" % kind
+    key = "wbc_hex_kernelILi%sELb0EJEE" % kind   # <KIND, false> with the empty pack: the tick without the acceleration rows, which the headline launches
     start = [i for i, l in enumerate(txt) if l.startswith("_Z") and key in l.split(":")[0] and ":" in l][0]
     end = [i for i in range(start, len(txt)) if txt[i].startswith(".Lfunc_end")][0]
     seg = collections.Counter(); segs = []

@@ -26,7 +26,7 @@ def kernels(so):
         m = re.match(r"^[0-9a-f]+ <(.*)>:", l)
         if m:
             cur = m.group(1); d[cur] = []; continue
-        if cur is not None and l:
+        if cur is not None and l and l != "...":       # ("...": the zero padding objdump shows behind a kernel that is not the last one)
             d[cur].append(re.sub(r"<.*?>", "", re.sub(r"\b0x[0-9a-f]+\b|\b[0-9]+\b(?=\s*$)", "N", l)))
     return d
 
@@ -37,6 +37,14 @@ if __name__ == "__main__":
         t = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()
         m = re.search(r"(\w+(<[^>]*>)?)\(", t.replace("(anonymous namespace)::", ""))
         return m.group(1) if m else t[:80]
+    # since round 20 wbc_hex_kernel<K, TB> is the tick WITHOUT the acceleration rows and wbc_hex_kernel<K, TB, VdotRows> the tick with them, which is
+    # what an older build calls wbc_hex_kernel<K, TB>: a build without any VdotRows kernel is read under the newer names
+    def named(d):
+        d = {dem(k): v for k, v in d.items()}
+        if any("VdotRows" in k for k in d):
+            return d
+        return {re.sub(r"^(wbc_hex_kernel<\d, \w+)>$", r"\1, VdotRows>", k): v for k, v in d.items()}
+    a, b = named(a), named(b)
     for k in sorted(set(a) | set(b)):
         na, nb = len(a.get(k, [])), len(b.get(k, []))
-        print("%-9s %6d %6d  %s" % ("same" if a.get(k) == b.get(k) else "DIFFERENT", na, nb, dem(k)))
+        print("%-9s %6d %6d  %s" % ("same" if a.get(k) == b.get(k) else ("only one" if not (na and nb) else "DIFFERENT"), na, nb, k))
