@@ -223,14 +223,16 @@ def fill_model(table, q_perm=None, act_perm=None):
     return m
 
 
-def dev_ptr(a, rows, n, tdt, name, device, owner, optional=False):
-    """Pointer to a contiguous CUDA tensor of dtype tdt and shape [rows, n] ([n] when rows is 0) on cuda:`device`, where `owner`
-    ("the plant", "this controller's handle") lives; None for an absent optional tensor."""
+def dev_ptr(a, rows, n, dtype, name, device, owner, optional=False):
+    """Pointer to a contiguous CUDA tensor of the dtype torch and numpy call `dtype` ("float64", "uint8", "int32") and shape [rows, n]
+    ([n] when rows is 0) on cuda:`device`, where `owner` ("the plant", "this controller's handle") lives; None for an absent optional
+    tensor."""
     import torch
     if a is None:
         if optional:
             return None
         raise ValueError(name + " is required")
+    tdt = getattr(torch, dtype)
     if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == tdt and a.is_contiguous()):
         raise ValueError("%s: expected a contiguous CUDA tensor of dtype %s" % (name, tdt))
     if a.device.index != device:
@@ -240,8 +242,72 @@ def dev_ptr(a, rows, n, tdt, name, device, owner, optional=False):
     return C.c_void_p(a.data_ptr())
 
 
+def new_out(rows, n, dtype, device, zero=False):
+    """A fresh output tensor of `dtype` (a name, as dev_ptr takes it) and shape [rows, n] ([n] when rows is 0) on `device`; zeroed where
+    the caller may see it unwritten."""
+    import torch
+    return (torch.zeros if zero else torch.empty)((rows, n) if rows else (n,), dtype=getattr(torch, dtype), device=device)
+
+
+def outputs(out, specs, n, device, owner, zero=False):
+    """The caller's `out` or fresh tensors -> (tensors, pointers).  specs: (rows, dtype, name) per tensor, in the order of `out`.  The
+    caller's tensors are checked as dev_ptr checks them; fresh ones live on cuda:`device`, zeroed if `zero`."""
+    if out is None:
+        ts = tuple(new_out(rows, n, dtype, device, zero) for rows, dtype, _ in specs)
+        return ts, [C.c_void_p(t.data_ptr()) for t in ts]
+    ts = tuple(out)
+    if len(ts) != len(specs):
+        raise ValueError("out: expected (%s)" % ", ".join(name for _, _, name in specs))
+    return ts, [dev_ptr(t, rows, n, dtype, name, device, owner) for t, (rows, dtype, name) in zip(ts, specs)]
+
+
+# the output sets more than one module allocates, as `outputs` takes them
+TICK_OUTS = ((12, "float64", "tau"), (4, "float64", "metrics"), (0, "int32", "status"))
+TARGET_OUTS = ((54, "float64", "targets"), (0, "uint8", "contact_mask"))
+
+
+_torch = None
+
+
+def stream_of(device):
+    """torch's current stream on cuda:`device`, as the integer hipStream_t.  Every tick asks: the module is looked up once."""
+    global _torch
+    if _torch is None:
+        import torch as _torch
+    return _torch.cuda.current_stream(device).cuda_stream
+
+
 def kernel_info(fn, handle):
     """The answer of a wbc_*_kernel_info entry point as a dict"""
     a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
     check(fn(handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
     return dict(num_regs=a.value, scratch_bytes_per_lane=b.value, lds_bytes=c.value, block_threads=d.value)
+
+
+class Handle:
+    """What the owners of a wbc_* handle share: the bound library `_L`, the handle `_h` and its device, the handle's lifetime, torch's
+    stream, kernel_info's answer.  A subclass names its wbc_*_destroy in `_destroy` and sets _L, _h and device in its __init__; the state
+    some of them add starts out absent here, so an object that never ran its __init__ answers like one that set nothing."""
+    _destroy = None
+    _L = _h = device = None
+    _keep = None                            # the controller's and the planner's: the tensors of the last call, kept alive
+    _terrain = None                         # GroundContactPlant's and GaitPlanner's: what set_terrain stored
+    _follow = "off"                         # GroundContactPlant's: set_follow's mode
+    _n = _schedule = _feedback = None       # GaitPlanner's: set_commands' N, set_schedule's arrays, set_feedback's (n, parameters)
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(stream_of(self.device))
+
+    def _kernel_info(self, entry_point):
+        return kernel_info(getattr(self._L, entry_point), self._h)

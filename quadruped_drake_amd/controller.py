@@ -59,8 +59,16 @@ STATUS_TEXT = {1: "iteration cap", 2: "not answerable -- singular, infeasible, o
                3: "ill-conditioned: |sin(knee)| < 1e-4 on a leg under a task-space law; torques written but not trustworthy"}
 
 
-class BatchedController:
+_OWNER = "this controller's handle"
+_NP = {"float64": np.float64, "uint8": np.uint8, "int32": np.int32}   # a host-pointer tick converts by type: numpy parses a name every time
+# (rows, dtype, name[, optional]) of a tick's arrays, in wbc_step's order; the dtype by the name numpy and torch share
+_TICK_INS = ((19, "float64", "q", False), (18, "float64", "v", False), (54, "float64", "targets", False),
+             (0, "uint8", "contact_mask", False), (0, "float64", "mu", True), (0, "float64", "mass_scale", True))
+
+
+class BatchedController(_lib.Handle):
     kind = None
+    _destroy = "wbc_destroy"
 
     def __init__(self, model="mini_cheetah", max_batch=4096, device=0, params=None, host_ptrs=False,
                  q_perm=None, act_perm=None, use_torch_stream=True, strict=False):
@@ -94,68 +102,48 @@ class BatchedController:
         `with torch.cuda.stream(s)` must not race with the stream it was created on)."""
         if not self._torch_stream:
             return None
-        import torch
-        s = torch.cuda.current_stream(self.device).cuda_stream
+        s = _lib.stream_of(self.device)
         if s != self._bound_stream:
             _lib.check(self._L.wbc_set_stream(self._h, C.c_void_p(s)))
             self._bound_stream = s
         return s
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.wbc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _adopt(self, stream, keep):
+        """After a wbc_*_rollout of a plant bound this handle to `stream` (plant.closed_loop): remember it, and keep the loop's arrays alive."""
+        self._bound_stream, self._keep = stream, keep
 
     # -- pointers ---------------------------------------------------------------------------
     def _ptr(self, a, rows, n, dtype, name, optional=False):
+        """-> (what to keep alive, its pointer): a CUDA tensor through the marshaller, or on a host-pointer handle anything numpy converts"""
+        if not self.host_ptrs:
+            return a, _lib.dev_ptr(a, rows, n, dtype, name, self.device, _OWNER, optional)
         if a is None:
             if optional:
                 return None, None
             raise ValueError(name + " is required")
-        if self.host_ptrs:
-            arr = np.ascontiguousarray(a, dtype=dtype)
-            if arr.shape != ((rows, n) if rows else (n,)):
-                raise ValueError("%s: expected shape %s, got %s" % (name, (rows, n) if rows else (n,), arr.shape))
-            return arr, C.c_void_p(arr.ctypes.data)
-        import torch
-        tdt = {np.float64: torch.float64, np.uint8: torch.uint8, np.int32: torch.int32}[dtype]
-        return a, _lib.dev_ptr(a, rows, n, tdt, name, self.device, "this controller's handle")
+        arr = np.ascontiguousarray(a, dtype=_NP[dtype])
+        if arr.shape != ((rows, n) if rows else (n,)):
+            raise ValueError("%s: expected shape %s, got %s" % (name, (rows, n) if rows else (n,), arr.shape))
+        return arr, C.c_void_p(arr.ctypes.data)
 
-    def _out(self, rows, n, dtype):
-        if self.host_ptrs:
-            arr = np.zeros((rows, n) if rows else (n,), dtype=dtype)
-            return arr, C.c_void_p(arr.ctypes.data)
-        import torch
-        tdt = {np.float64: torch.float64, np.int32: torch.int32}[dtype]
-        t = torch.empty((rows, n) if rows else (n,), dtype=tdt, device="cuda:%d" % self.device)
-        return t, C.c_void_p(t.data_ptr())
+    def _outs(self, out, specs, n):
+        """The caller's `out` or fresh arrays -> (arrays, pointers)"""
+        if not self.host_ptrs:
+            return _lib.outputs(out, specs, n, self.device, _OWNER)
+        if out is None:
+            arrs = [np.zeros((rows, n) if rows else (n,), dtype=_NP[dtype]) for rows, dtype, _ in specs]
+            return tuple(arrs), [C.c_void_p(a.ctypes.data) for a in arrs]
+        pairs = [self._ptr(a, rows, n, dtype, name) for a, (rows, dtype, name) in zip(out, specs, strict=True)]
+        return tuple(k for k, _ in pairs), [p for _, p in pairs]
 
     def _args(self, q, v, targets, contact_mask, mu, mass_scale, out):
         n = int(q.shape[1])
-        keep = []
-        ptrs = []
-        for a, rows, dt, name, opt in ((q, 19, np.float64, "q", False), (v, 18, np.float64, "v", False),
-                                       (targets, 54, np.float64, "targets", False),
-                                       (contact_mask, 0, np.uint8, "contact_mask", False),
-                                       (mu, 0, np.float64, "mu", True), (mass_scale, 0, np.float64, "mass_scale", True)):
-            k, p = self._ptr(a, rows, n, dt, name, opt)
+        keep, ptrs = [], []
+        for a, (rows, dtype, name, opt) in zip((q, v, targets, contact_mask, mu, mass_scale), _TICK_INS):
+            k, p = self._ptr(a, rows, n, dtype, name, opt)
             keep.append(k); ptrs.append(p)
-        if out is None:
-            tau, pt = self._out(12, n, np.float64)
-            met, pm = self._out(4, n, np.float64)
-            st, ps = self._out(0, n, np.int32)
-        else:
-            tau, met, st = out
-            tau, pt = self._ptr(tau, 12, n, np.float64, "tau")
-            met, pm = self._ptr(met, 4, n, np.float64, "metrics")
-            st, ps = self._ptr(st, 0, n, np.int32, "status")
-        return n, keep, ptrs + [pt, pm, ps], (tau, met, st)
+        outs, pouts = self._outs(out, _lib.TICK_OUTS, n)
+        return n, keep, ptrs + pouts, outs
 
     # -- the hot path -----------------------------------------------------------------------
     def step(self, q, v, targets, contact_mask, mu=None, mass_scale=None, out=None):
@@ -240,37 +228,31 @@ class BatchedController:
             _lib.check(self._L.wbc_set_vdot_output(self._h, None))
             return
         n = int(vdot.shape[1]) if n is None else int(n)
-        k, p = self._ptr(vdot, 18, n, np.float64, "vdot")
+        k, p = self._ptr(vdot, 18, n, "float64", "vdot")
         self._vdot = k
         _lib.check(self._L.wbc_set_vdot_output(self._h, p))
 
     def integrate(self, q, v, vdot, dt):
         """Semi-implicit Euler step, in place on q [19, N] and v [18, N]."""
         n = int(q.shape[1])
-        _, pq = self._ptr(q, 19, n, np.float64, "q")
-        _, pv = self._ptr(v, 18, n, np.float64, "v")
-        _, pd = self._ptr(vdot, 18, n, np.float64, "vdot")
+        _, pq = self._ptr(q, 19, n, "float64", "q")
+        _, pv = self._ptr(v, 18, n, "float64", "v")
+        _, pd = self._ptr(vdot, 18, n, "float64", "vdot")
         self._bind_stream()
         _lib.check(self._L.wbc_integrate(self._h, n, n, float(dt), pq, pv, pd))
 
     def rollout(self, traj, steps, dt, q, v, time, mu=None, mass_scale=None):
         """`steps` closed-loop ticks on the device: lookup(traj, time) -> step -> integrate.  Updates q, v, time in
         place; returns the last (tau, metrics, status, targets, mask)."""
-        import torch
         n = int(q.shape[1])
-        _, pq = self._ptr(q, 19, n, np.float64, "q")
-        _, pv = self._ptr(v, 18, n, np.float64, "v")
-        _, pt = self._ptr(time, 0, n, np.float64, "time")
-        _, pmu = self._ptr(mu, 0, n, np.float64, "mu", optional=True)
-        _, pms = self._ptr(mass_scale, 0, n, np.float64, "mass_scale", optional=True)
-        dev = q.device
-        tg = torch.empty((54, n), dtype=torch.float64, device=dev); mk = torch.empty((n,), dtype=torch.uint8, device=dev)
-        tau = torch.empty((12, n), dtype=torch.float64, device=dev); met = torch.empty((4, n), dtype=torch.float64, device=dev)
-        st = torch.empty((n,), dtype=torch.int32, device=dev); vd = torch.empty((18, n), dtype=torch.float64, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
+        _, pq = self._ptr(q, 19, n, "float64", "q")
+        _, pv = self._ptr(v, 18, n, "float64", "v")
+        _, pt = self._ptr(time, 0, n, "float64", "time")
+        _, pmu = self._ptr(mu, 0, n, "float64", "mu", optional=True)
+        _, pms = self._ptr(mass_scale, 0, n, "float64", "mass_scale", optional=True)
+        (tg, mk, tau, met, st, vd), (ptg, pmk, *pouts) = self._outs(None, _lib.TARGET_OUTS + _lib.TICK_OUTS + ((18, "float64", "vdot"),), n)
         self._bind_stream()
-        _lib.check(self._L.wbc_rollout(self._h, traj._h, int(steps), float(dt), n, n, pq, pv, pt, p(tg), p(mk),
-                                       pmu, pms, p(tau), p(met), p(st), p(vd)))
+        _lib.check(self._L.wbc_rollout(self._h, traj._h, int(steps), float(dt), n, n, pq, pv, pt, ptg, pmk, pmu, pms, *pouts))
         self._keep = (tg, mk, tau, met, st, vd, mu, mass_scale)
         return tau, met, st, tg, mk
 
@@ -294,7 +276,7 @@ class BatchedController:
 
     def kernel_info(self, rollout=False):
         """Registers, scratch bytes per lane and LDS bytes of the tick kernel (rollout=True: of the persistent closed-loop kernel)."""
-        return _lib.kernel_info(self._L.wbc_rollout_kernel_info if rollout else self._L.wbc_kernel_info, self._h)
+        return self._kernel_info("wbc_rollout_kernel_info" if rollout else "wbc_kernel_info")
 
     # -- single-robot convenience with the reference's signature --------------------------
     def ControlLaw(self, q, v, trunk_data):

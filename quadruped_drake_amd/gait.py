@@ -15,10 +15,11 @@ shifts every swing's landing point by what the measured trunk velocity asks for,
 Torch tensors and torch's current stream, as in controller.py and plant.py.
 """
 import ctypes as C
+import operator
 
 import numpy as np
 
-from . import _lib, workloads
+from . import _lib, terrain, workloads
 
 FEET = ("LF", "RF", "LH", "RH")   # bit i of a contact mask (towr/include/towr/models/endeffector_mappings.h: enum QuadrupedIDs)
 # towr/src/quadruped_gait_generator.cc:50-70 names a contact state by two letters, hind legs then front legs: I none, P the left
@@ -124,13 +125,19 @@ def c_terrain_params(body="fit", max_grade=0.5, edge_margin=0.03, apex_max=0.25)
     return p
 
 
-class GaitPlanner:
+def _dev_ptr(a, rows, n, dtype, name, device, optional=False):
+    return _lib.dev_ptr(a, rows, n, dtype, name, device, "the planner", optional)
+
+
+class GaitPlanner(_lib.Handle):
     """The targets of N walking robots, each with its own command (include/wbc_gait.h).
 
     model: a name of workloads.STAND_FEET, which gives the nominal stance and height (or pass stance [4, 2] and height);
     strides: up to 16 strides, names of STRIDES or (durations, masks) pairs; instance i walks strides[gait_id[i]].
     swing_height [m]; ramp_time [s]: the body reaches its commanded velocity smoothly over this time, stepping in place at first;
     wait_time [s]: standing targets before it, as the trajectories have it."""
+
+    _destroy = "wbc_gait_destroy"
 
     def __init__(self, model="mini_cheetah", strides=("trot",), swing_height=0.05, ramp_time=0.5, wait_time=0.0, device=0, stance=None,
                  height=None):
@@ -144,12 +151,6 @@ class GaitPlanner:
         self.params = c_params(stance, height, swing_height, ramp_time, wait_time)
         self.device = int(device)
         self._L = _lib.lib()
-        self._h = None
-        self._n = None
-        self._keep = None
-        self._terrain = None
-        self._schedule = None
-        self._feedback = None
         h = C.c_void_p()
         _lib.check(self._L.wbc_gait_create(C.byref(self.params), c_strides(self.strides), len(self.strides), self.device, C.byref(h)))
         self._h = h
@@ -162,10 +163,10 @@ class GaitPlanner:
         if not (isinstance(cmd, torch.Tensor) and cmd.dim() == 2):
             raise ValueError("cmd: expected a CUDA tensor of shape [3, N]")
         n, d = int(cmd.shape[1]), self.device
-        pc = _lib.dev_ptr(cmd, 3, n, torch.float64, "cmd", d, "the planner")
-        pg = _lib.dev_ptr(gait_id, 0, n, torch.uint8, "gait_id", d, "the planner", True)
-        ps = _lib.dev_ptr(stride_scale, 0, n, torch.float64, "stride_scale", d, "the planner", True)
-        p0 = _lib.dev_ptr(start, 3, n, torch.float64, "start", d, "the planner", True)
+        pc = _dev_ptr(cmd, 3, n, "float64", "cmd", d)
+        pg = _dev_ptr(gait_id, 0, n, "uint8", "gait_id", d, True)
+        ps = _dev_ptr(stride_scale, 0, n, "float64", "stride_scale", d, True)
+        p0 = _dev_ptr(start, 3, n, "float64", "start", d, True)
         _lib.check(self._L.wbc_gait_set_commands(self._h, pc, pg, ps, p0))
         self._n, self._keep = n, (cmd, gait_id, stride_scale, start)
 
@@ -181,11 +182,10 @@ class GaitPlanner:
             raise ValueError("GaitPlanner.set_schedule: set_commands first")
         n, d = self._n, self.device
         m, when, c = schedule_arrays(times, cmds, n, self.params.ramp_time)
-        dev = "cuda:%d" % d
-        tm, tw, tc = (torch.tensor(a, device=dev) for a in (m, when, c))
-        s = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
-        _lib.check(self._L.wbc_gait_set_schedule(self._h, s, n, n, float(blend), C.c_void_p(tm.data_ptr()), C.c_void_p(tw.data_ptr()),
-                                                 C.c_void_p(tc.data_ptr())))
+        tm, tw, tc = (torch.tensor(a, device="cuda:%d" % d) for a in (m, when, c))      # alive until the call has synchronised
+        _lib.check(self._L.wbc_gait_set_schedule(self._h, self._stream(), n, n, float(blend), _dev_ptr(tm, 0, n, "uint8", "nswitch", d),
+                                                 _dev_ptr(tw, MAX_SWITCHES, n, "float64", "when", d),
+                                                 _dev_ptr(tc, 3 * MAX_SWITCHES, n, "float64", "cmds", d)))
         self._schedule = (m, when, c, float(blend))
 
     def clear_schedule(self):
@@ -195,7 +195,7 @@ class GaitPlanner:
 
     @property
     def has_schedule(self):
-        return getattr(self, "_schedule", None) is not None
+        return self._schedule is not None
 
     def schedule_kernel_info(self, terrain=False):
         """kernel_info() of the kernel that runs while a schedule is set, without or with a terrain."""
@@ -228,50 +228,38 @@ class GaitPlanner:
 
     @property
     def has_feedback(self):
-        return getattr(self, "_feedback", None) is not None
+        return self._feedback is not None
 
     def feedback_kernel_info(self):
         """kernel_info() of the feedback pass's kernel."""
-        return _lib.kernel_info(self._L.wbc_gait_feedback_kernel_info, self._h)
+        return self._kernel_info("wbc_gait_feedback_kernel_info")
 
     def targets_measured(self, time, q, v, out=None, offsets=None):
         """targets(time, out), then the feedback pass on the measured q [19, N] and v [18, N]: the foot rows shifted, the state
         advanced by one call.  offsets: an optional [8, N] float64 tensor that receives the (x, y) offset of each foot.  Needs
         set_feedback.  Asynchronous on torch's current stream."""
-        import torch
         if self._n is None:
             raise ValueError("GaitPlanner.targets_measured: set_commands first")
         n, d = self._n, self.device
-        pt = _lib.dev_ptr(time, 0, n, torch.float64, "time", d, "the planner")
-        pq = _lib.dev_ptr(q, 19, n, torch.float64, "q", d, "the planner")
-        pv = _lib.dev_ptr(v, 18, n, torch.float64, "v", d, "the planner")
-        if out is None:
-            out = (torch.empty((54, n), dtype=torch.float64, device="cuda:%d" % d), torch.empty((n,), dtype=torch.uint8, device="cuda:%d" % d))
-        tg, mk = out
-        ptg = _lib.dev_ptr(tg, 54, n, torch.float64, "targets", d, "the planner")
-        pmk = _lib.dev_ptr(mk, 0, n, torch.uint8, "contact_mask", d, "the planner")
-        pof = _lib.dev_ptr(offsets, 8, n, torch.float64, "offsets", d, "the planner", True)
-        s = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
-        _lib.check(self._L.wbc_gait_targets_measured(self._h, s, n, n, pt, pq, pv, ptg, pmk, pof))
-        return tg, mk
+        pt = _dev_ptr(time, 0, n, "float64", "time", d)
+        pq = _dev_ptr(q, 19, n, "float64", "q", d)
+        pv = _dev_ptr(v, 18, n, "float64", "v", d)
+        outs, pouts = _lib.outputs(out, _lib.TARGET_OUTS, n, d, "the planner")
+        pof = _dev_ptr(offsets, 8, n, "float64", "offsets", d, True)
+        _lib.check(self._L.wbc_gait_targets_measured(self._h, self._stream(), n, n, pt, pq, pv, *pouts, pof))
+        return outs
 
     def targets(self, time, out=None):
         """-> (targets [54, N] float64, contact_mask [N] uint8) at time [N] float64; out: such a pair to write into.  Asynchronous on
         torch's current stream."""
-        import torch
         if self._n is None:
             raise ValueError("GaitPlanner.targets: set_commands first")
         n, d = self._n, self.device
         self._check_terrain_n(n)
-        pt = _lib.dev_ptr(time, 0, n, torch.float64, "time", d, "the planner")
-        if out is None:
-            out = (torch.empty((54, n), dtype=torch.float64, device="cuda:%d" % d), torch.empty((n,), dtype=torch.uint8, device="cuda:%d" % d))
-        tg, mk = out
-        ptg = _lib.dev_ptr(tg, 54, n, torch.float64, "targets", d, "the planner")
-        pmk = _lib.dev_ptr(mk, 0, n, torch.uint8, "contact_mask", d, "the planner")
-        s = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
-        _lib.check(self._L.wbc_gait_targets(self._h, s, n, n, pt, ptg, pmk))
-        return tg, mk
+        pt = _dev_ptr(time, 0, n, "float64", "time", d)
+        outs, pouts = _lib.outputs(out, _lib.TARGET_OUTS, n, d, "the planner")
+        _lib.check(self._L.wbc_gait_targets(self._h, self._stream(), n, n, pt, *pouts))
+        return outs
 
     def set_terrain(self, profiles, terrain_id=None, terrain_scale=None, body="fit", max_grade=0.5, edge_margin=0.03, apex_max=0.25):
         """Make the planner's targets the finished targets on a terrain (include/wbc_gait_terrain.h): footholds on the
@@ -280,23 +268,12 @@ class GaitPlanner:
         roll.  profiles: 1 .. 16 terrain.Profile, what GroundContactPlant.set_terrain takes; instance i walks on
         profiles[terrain_id[i]] (uint8 [N]; None: profile 0) scaled by terrain_scale[i] (float64 [N]; None: 1.0); the tensors are kept
         alive here.  No follow pass may run after such targets.  Synchronises the device."""
-        import torch
-        from . import terrain as _terrain
         if body not in BODY_MODES:
             raise ValueError("body %r: expected one of %s" % (body, ", ".join(BODY_MODES)))
-        profiles = list(profiles) if profiles is not None else []
-        if not profiles or not all(isinstance(p, _terrain.Profile) for p in profiles):
-            raise ValueError("set_terrain: profiles must be a non-empty list of terrain.Profile (clear_terrain() takes the terrain away)")
-        n = None
-        for a in (terrain_id, terrain_scale):
-            if a is not None and isinstance(a, torch.Tensor) and a.dim() == 1:
-                n = int(a.shape[0]) if n is None else n
-        pid = _lib.dev_ptr(terrain_id, 0, n, torch.uint8, "terrain_id", self.device, "the planner", True)
-        psc = _lib.dev_ptr(terrain_scale, 0, n, torch.float64, "terrain_scale", self.device, "the planner", True)
+        *args, stored = terrain.bind(profiles, terrain_id, terrain_scale, self.device, "the planner", " (clear_terrain() takes the terrain away)")
         tp = c_terrain_params(body, max_grade, edge_margin, apex_max)
-        arr = _terrain.c_array(profiles)
-        _lib.check(self._L.wbc_gait_set_terrain(self._h, C.byref(tp), C.cast(arr, C.c_void_p), len(profiles), pid, psc))
-        self._terrain = (profiles, terrain_id, terrain_scale, n, body)
+        _lib.check(self._L.wbc_gait_set_terrain(self._h, C.byref(tp), *args))
+        self._terrain = stored + (body,)
 
     def clear_terrain(self):
         """The plain gait again: targets about the plane z = 0, the kernel a planner without a terrain launches."""
@@ -304,33 +281,20 @@ class GaitPlanner:
         self._terrain = None
 
     def _check_terrain_n(self, n):
-        t = getattr(self, "_terrain", None)
-        if t is not None and t[3] is not None and t[3] != n:
-            raise ValueError("the GaitPlanner's terrain_id / terrain_scale hold %d instances, the call has %d" % (t[3], n))
+        terrain._check_terrain_n(self._terrain, n, operator.ne, "the GaitPlanner's ")   # the planner's terrain is set for one batch size
 
     @property
     def has_terrain(self):
-        return getattr(self, "_terrain", None) is not None
+        return self._terrain is not None
 
     def kernel_info(self):
         """Registers, scratch bytes per lane, LDS bytes and threads per block of the gait kernel."""
-        return _lib.kernel_info(self._L.wbc_gait_kernel_info, self._h)
+        return self._kernel_info("wbc_gait_kernel_info")
 
     def terrain_kernel_info(self):
         """kernel_info() of the kernel that runs while a terrain is set."""
-        return _lib.kernel_info(self._L.wbc_gait_terrain_kernel_info, self._h)
+        return self._kernel_info("wbc_gait_terrain_kernel_info")
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._L.wbc_gait_destroy(self._h)
-            self._h = None
-            self._keep = None
-            self._terrain = None
-            self._schedule = None
-            self._feedback = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
+        self._keep = self._terrain = self._schedule = self._feedback = None

@@ -39,49 +39,34 @@ def encode_robot_state(q=None, v=None, tau=None):
     return out.raw
 
 
-def _msgs_tensor(messages, device):
-    import torch
-    if isinstance(messages, torch.Tensor):
-        t = messages
-    else:
-        raw = messages if isinstance(messages, (bytes, bytearray)) else b"".join(messages)
-        t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
-    if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 1 and t.numel() % MESSAGE_BYTES == 0):
-        raise ValueError("messages: a contiguous uint8 CUDA tensor (or bytes) holding whole 204-byte messages")
-    return t
+_OWNER = "the codec"
 
 
 def unpack_states(messages, device=0, out=None):
     """messages: bytes / list of bytes / uint8 CUDA tensor [N * 204] -> (q [19, N], v [18, N], ok [N] uint8) on the device,
     asynchronously on torch's current stream.  ok[i] = 0: foreign fingerprint, that robot's columns are left as they were."""
     import torch
-    dev = "cuda:%d" % device
-    t = _msgs_tensor(messages, dev)
-    n = t.numel() // MESSAGE_BYTES
-    if out is None:
-        out = (torch.zeros((19, n), dtype=torch.float64, device=dev), torch.zeros((18, n), dtype=torch.float64, device=dev))
-    q, v = out
-    if not all(x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() for x in (q, v)) or \
-            tuple(q.shape) != (19, n) or tuple(v.shape) != (18, n):
-        raise ValueError("out: (float64 [19, N], float64 [18, N]) contiguous CUDA tensors")
-    ok = torch.empty((n,), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    _lib.check(_lib.lib().wbc_robot_states_unpack(device, C.c_void_p(stream), n, n, C.c_void_p(t.data_ptr()),
-                                                  C.c_void_p(q.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(ok.data_ptr())))
+    if not isinstance(messages, torch.Tensor):
+        raw = messages if isinstance(messages, (bytes, bytearray)) else b"".join(messages)
+        messages = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to("cuda:%d" % device)
+    n, rest = divmod(messages.numel(), MESSAGE_BYTES)
+    if rest:
+        raise ValueError("messages: a contiguous uint8 CUDA tensor (or bytes) holding whole 204-byte messages")
+    pm = _lib.dev_ptr(messages, 0, n * MESSAGE_BYTES, "uint8", "messages", device, _OWNER)
+    (q, v), (pq, pv) = _lib.outputs(out, ((19, "float64", "q"), (18, "float64", "v")), n, device, _OWNER, zero=True)
+    (ok,), (pok,) = _lib.outputs(None, ((0, "uint8", "ok"),), n, device, _OWNER)
+    _lib.check(_lib.lib().wbc_robot_states_unpack(device, C.c_void_p(_lib.stream_of(device)), n, n, pm, pq, pv, pok))
     return q, v, ok
 
 
 def pack_controls(tau, q_perm=None, act_perm=None):
     """tau: float64 CUDA tensor [12, N] in actuator order -> uint8 CUDA tensor [N * 204] of "robot_control_input" messages."""
     import torch
-    if not (isinstance(tau, torch.Tensor) and tau.is_cuda and tau.dtype == torch.float64 and tau.is_contiguous() and
-            tau.dim() == 2 and tau.shape[0] == 12):
+    if not (isinstance(tau, torch.Tensor) and tau.is_cuda and tau.dim() == 2):
         raise ValueError("tau: a contiguous float64 CUDA tensor [12, N]")
-    n = int(tau.shape[1])
-    device = tau.device.index
-    msgs = torch.empty((n * MESSAGE_BYTES,), dtype=torch.uint8, device=tau.device)
+    n, device = int(tau.shape[1]), tau.device.index
+    pt = _lib.dev_ptr(tau, 12, n, "float64", "tau", device, _OWNER)
+    (msgs,), (pm,) = _lib.outputs(None, ((0, "uint8", "messages"),), n * MESSAGE_BYTES, device, _OWNER)
     arr = lambda p: None if p is None else (C.c_int * 12)(*[int(x) for x in p])
-    stream = torch.cuda.current_stream(device).cuda_stream
-    _lib.check(_lib.lib().wbc_robot_controls_pack(device, C.c_void_p(stream), n, n, C.c_void_p(tau.data_ptr()), arr(q_perm),
-                                                  arr(act_perm), C.c_void_p(msgs.data_ptr())))
+    _lib.check(_lib.lib().wbc_robot_controls_pack(device, C.c_void_p(_lib.stream_of(device)), n, n, pt, arr(q_perm), arr(act_perm), pm))
     return msgs

@@ -25,20 +25,11 @@ class BasicController:
 
     def step(self, q, v, out=None):
         """q [19, N], v [18, N] float64 CUDA tensors -> tau [12, N] in actuator order, asynchronously on torch's current stream."""
-        import torch
-        n = int(q.shape[1])
-        for t, rows, name in ((q, 19, "q"), (v, 18, "v")):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-                    and tuple(t.shape) == (rows, n) and t.device.index == self.device):
-                raise ValueError("%s: expected a contiguous float64 CUDA tensor [%d, N] on device %d" % (name, rows, self.device))
-        if out is None:
-            out = torch.empty((12, n), dtype=torch.float64, device=q.device)
-        elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (12, n)):
-            raise ValueError("out: expected a contiguous float64 CUDA tensor [12, N]")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(_lib.lib().wbc_pd_step(self.device, C.c_void_p(stream), n, n, C.c_void_p(q.data_ptr()), C.c_void_p(v.data_ptr()),
-                                          self.q_nom.ctypes.data_as(_lib.c_double_p), self.kp, self.kd, self.u_max, self._qp, self._ap,
-                                          C.c_void_p(out.data_ptr())))
+        n, d = int(q.shape[1]), self.device
+        pq, pv = (_lib.dev_ptr(t, rows, n, "float64", name, d, "the controller") for t, rows, name in ((q, 19, "q"), (v, 18, "v")))
+        (out,), (po,) = _lib.outputs(None if out is None else (out,), ((12, "float64", "out"),), n, d, "the controller")
+        _lib.check(_lib.lib().wbc_pd_step(d, C.c_void_p(_lib.stream_of(d)), n, n, pq, pv, self.q_nom.ctypes.data_as(_lib.c_double_p),
+                                          self.kp, self.kd, self.u_max, self._qp, self._ap, po))
         return out
 
     def ControlLaw(self, q, v):

@@ -15,10 +15,11 @@ either plant.
 import contextlib
 import ctypes as C
 import math
+import operator
 
-from . import _lib
+from . import _lib, terrain
 from ._lib import WbcGroundParams, WbcPlantParams  # noqa: F401 (the mirrors of wbc_plant_params / wbc_ground_params, under their names here)
-from .controller import load_model
+from .controller import BatchedController, load_model
 
 PULL, CONE, CLIP, BAD = 1, 2, 4, 8
 SLIP, FELL = 1, 2   # GroundContactPlant's bits 0 and 1 (CLIP and BAD as above)
@@ -37,17 +38,25 @@ def _follow_mode(mode):
 _L = _lib.lib   # libwbc_hip.so, bound (the prototypes of every header: _lib.PROTOTYPES)
 
 
-def _dev_ptr(a, rows, n, tdt, name, device, optional=False):
-    return _lib.dev_ptr(a, rows, n, tdt, name, device, "the plant", optional)
+def _dev_ptr(a, rows, n, dtype, name, device, optional=False):
+    return _lib.dev_ptr(a, rows, n, dtype, name, device, "the plant", optional)
+
+
+def _outputs(out, specs, n, device):
+    return _lib.outputs(out, specs, n, device, "the plant")
 
 
 _wbc_model = _lib.fill_model
 
+# the plants' output sets, as _lib.outputs takes them, in the order of the entry points' arguments
+_RIGID_OUTS = ((18, "float64", "vdot"), (12, "float64", "force"), (0, "int32", "flags"))
+_RIGID_LOOP_OUTS = _RIGID_OUTS[1:]
+_GROUND_OUTS = ((18, "float64", "vdot"), (12, "float64", "force"), (0, "uint8", "contact"), (0, "int32", "flags"))
+_GROUND_STEP_OUTS = _GROUND_OUTS[1:]
 
-class _Plant:
-    """What the two plants share: the model table and its wbc_model, the handle's lifetime, torch's stream, kernel_info's answer.
-    A subclass names its wbc_*_destroy in `_destroy` and sets self._h in its __init__."""
-    _destroy = None
+
+class _Plant(_lib.Handle):
+    """What the two plants share beyond _lib.Handle: the model table and its wbc_model.  A subclass sets self._h in its __init__."""
 
     def _open(self, model, device, q_perm, act_perm):
         """-> (the bound library, the wbc_model of `model`)"""
@@ -55,24 +64,6 @@ class _Plant:
         self.device = int(device)
         self._L = _L()
         return self._L, _wbc_model(self.table, q_perm, act_perm)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            getattr(self._L, self._destroy)(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _kernel_info(self, fn):
-        return _lib.kernel_info(fn, self._h)
 
 
 class RigidContactPlant(_Plant):
@@ -92,49 +83,33 @@ class RigidContactPlant(_Plant):
         _lib.check(L.wbc_plant_create(C.byref(m), C.byref(p), self.device, C.byref(h)))
         self._h = h
 
-    def _outs(self, n, out):
-        import torch
-        if out is not None:
-            return out
-        dev = "cuda:%d" % self.device
-        return (torch.empty((18, n), dtype=torch.float64, device=dev), torch.empty((12, n), dtype=torch.float64, device=dev),
-                torch.empty((n,), dtype=torch.int32, device=dev))
-
     def _inputs(self, q, v, tau, contact_mask, mu, mass_scale):
-        import torch
         n = int(q.shape[1])
         d = self.device
-        return n, [_dev_ptr(q, 19, n, torch.float64, "q", d), _dev_ptr(v, 18, n, torch.float64, "v", d),
-                   _dev_ptr(tau, 12, n, torch.float64, "tau", d), _dev_ptr(contact_mask, 0, n, torch.uint8, "contact_mask", d),
-                   _dev_ptr(mu, 0, n, torch.float64, "mu", d, True), _dev_ptr(mass_scale, 0, n, torch.float64, "mass_scale", d, True)]
+        return n, [_dev_ptr(q, 19, n, "float64", "q", d), _dev_ptr(v, 18, n, "float64", "v", d),
+                   _dev_ptr(tau, 12, n, "float64", "tau", d), _dev_ptr(contact_mask, 0, n, "uint8", "contact_mask", d),
+                   _dev_ptr(mu, 0, n, "float64", "mu", d, True), _dev_ptr(mass_scale, 0, n, "float64", "mass_scale", d, True)]
 
     def forward(self, q, v, tau, contact_mask, mu=None, mass_scale=None, out=None):
         """-> (vdot[18, N], force[12, N], flags[N]); q and v are not changed.  Asynchronous on torch's current stream."""
-        import torch
         n, ins = self._inputs(q, v, tau, contact_mask, mu, mass_scale)
-        vd, f, fl = self._outs(n, out)
-        outs = [_dev_ptr(vd, 18, n, torch.float64, "vdot", self.device), _dev_ptr(f, 12, n, torch.float64, "force", self.device),
-                _dev_ptr(fl, 0, n, torch.int32, "flags", self.device)]
-        _lib.check(self._L.wbc_plant_forward(self._h, self._stream(), n, n, *ins, *outs))
-        return vd, f, fl
+        outs, pouts = _outputs(out, _RIGID_OUTS, n, self.device)
+        _lib.check(self._L.wbc_plant_forward(self._h, self._stream(), n, n, *ins, *pouts))
+        return outs
 
     def step(self, q, v, tau, contact_mask, dt, time=None, mu=None, mass_scale=None, counts=None, out=None):
         """forward, then the semi-implicit Euler step in place on q, v (time += dt when given; counts[4, N] int32: row b += 1
         when flag bit b is raised).  -> (vdot, force, flags)"""
-        import torch
         n, ins = self._inputs(q, v, tau, contact_mask, mu, mass_scale)
-        vd, f, fl = self._outs(n, out)
-        d = self.device
-        pt = _dev_ptr(time, 0, n, torch.float64, "time", d, True)
-        pc = _dev_ptr(counts, 4, n, torch.int32, "counts", d, True)
-        outs = [_dev_ptr(vd, 18, n, torch.float64, "vdot", d), _dev_ptr(f, 12, n, torch.float64, "force", d),
-                _dev_ptr(fl, 0, n, torch.int32, "flags", d)]
-        _lib.check(self._L.wbc_plant_step(self._h, self._stream(), n, n, float(dt), ins[0], ins[1], pt, *ins[2:], *outs, pc))
-        return vd, f, fl
+        pt = _dev_ptr(time, 0, n, "float64", "time", self.device, True)
+        pc = _dev_ptr(counts, 4, n, "int32", "counts", self.device, True)
+        outs, pouts = _outputs(out, _RIGID_OUTS, n, self.device)
+        _lib.check(self._L.wbc_plant_step(self._h, self._stream(), n, n, float(dt), ins[0], ins[1], pt, *ins[2:], *pouts, pc))
+        return outs
 
     def kernel_info(self):
         """Registers, scratch bytes per lane, LDS bytes and threads per block of the plant-step kernel."""
-        return self._kernel_info(self._L.wbc_plant_kernel_info)
+        return self._kernel_info("wbc_plant_kernel_info")
 
 
 class GroundContactPlant(_Plant):
@@ -160,7 +135,6 @@ class GroundContactPlant(_Plant):
         h = C.c_void_p()
         _lib.check(L.wbc_ground_create(C.byref(m), C.byref(p), self.device, C.byref(h)))
         self._h = h
-        self._terrain = None
 
     def close(self):
         super().close()
@@ -171,36 +145,24 @@ class GroundContactPlant(_Plant):
         again.  Instance i stands on profiles[terrain_id[i]] (uint8 [N] on the plant's device; None: profile 0) scaled in height
         by terrain_scale[i] (float64 [N]; None: 1.0).  Both tensors must cover the N of every later forward / step / closed_loop
         and are kept alive here.  An id beyond the list or a non-finite scale makes the instance BAD.  Synchronises the device."""
-        import torch
         if profiles is None:
             if terrain_id is not None or terrain_scale is not None:
                 raise ValueError("set_terrain: terrain_id / terrain_scale need profiles")
             _lib.check(self._L.wbc_ground_set_terrain(self._h, None, 0, None, None))
             self._terrain = None
             return
-        from . import terrain as _terrain
-        profiles = list(profiles)
-        if not profiles or not all(isinstance(p, _terrain.Profile) for p in profiles):
-            raise ValueError("set_terrain: profiles must be a non-empty list of terrain.Profile")
-        n = None
-        for a in (terrain_id, terrain_scale):
-            if a is not None and isinstance(a, torch.Tensor) and a.dim() == 1:
-                n = int(a.shape[0]) if n is None else n
-        pid = _dev_ptr(terrain_id, 0, n, torch.uint8, "terrain_id", self.device, True)
-        psc = _dev_ptr(terrain_scale, 0, n, torch.float64, "terrain_scale", self.device, True)
-        arr = _terrain.c_array(profiles)
-        _lib.check(self._L.wbc_ground_set_terrain(self._h, C.cast(arr, C.c_void_p), len(profiles), pid, psc))
-        self._terrain = (profiles, terrain_id, terrain_scale, n)
+        *args, stored = terrain.bind(profiles, terrain_id, terrain_scale, self.device, "the plant")
+        _lib.check(self._L.wbc_ground_set_terrain(self._h, *args))
+        self._terrain = stored
 
     def follow_targets(self, targets, mode="fit"):
         """Make targets [54, N] follow the terrain set on this plant, in place (include/wbc_ground.h, "Following the ground"):
         "lift" raises every foot target onto the surface under it and the body target onto the line fitted through the four planned
         footholds; "fit" also turns the body's attitude with that line; "off" does nothing.  Without a terrain nothing is launched.
         Asynchronous on torch's current stream.  -> targets"""
-        import torch
         n = int(targets.shape[1])
         self._check_terrain_n(n)
-        pt = _dev_ptr(targets, 54, n, torch.float64, "targets", self.device)
+        pt = _dev_ptr(targets, 54, n, "float64", "targets", self.device)
         _lib.check(self._L.wbc_ground_follow_targets(self._h, self._stream(), n, n, _follow_mode(mode), pt))
         return targets
 
@@ -212,64 +174,50 @@ class GroundContactPlant(_Plant):
 
     def follow_kernel_info(self):
         """kernel_info() of the kernel behind follow_targets."""
-        return self._kernel_info(self._L.wbc_ground_follow_kernel_info)
+        return self._kernel_info("wbc_ground_follow_kernel_info")
 
     def _check_terrain_n(self, n):
-        if self._terrain is not None and self._terrain[3] is not None and self._terrain[3] < n:
-            raise ValueError("terrain_id / terrain_scale hold %d instances, the call has %d" % (self._terrain[3], n))
+        terrain._check_terrain_n(self._terrain, n, operator.lt)     # a call may take the first n of a longer terrain
 
     def substeps(self, dt):
         """The number of explicit substeps wbc_ground_step takes for a period dt."""
         return max(1, int(math.ceil(float(dt) / self.params.max_substep * (1.0 - 1e-12))))
 
     def _inputs(self, q, v, tau, mu, mass_scale, ext_wrench):
-        import torch
         n = int(q.shape[1])
         d = self.device
         self._check_terrain_n(n)
-        return n, [_dev_ptr(q, 19, n, torch.float64, "q", d), _dev_ptr(v, 18, n, torch.float64, "v", d),
-                   _dev_ptr(tau, 12, n, torch.float64, "tau", d), _dev_ptr(mu, 0, n, torch.float64, "mu", d, True),
-                   _dev_ptr(mass_scale, 0, n, torch.float64, "mass_scale", d, True),
-                   _dev_ptr(ext_wrench, 6, n, torch.float64, "ext_wrench", d, True)]
+        return n, [_dev_ptr(q, 19, n, "float64", "q", d), _dev_ptr(v, 18, n, "float64", "v", d),
+                   _dev_ptr(tau, 12, n, "float64", "tau", d), _dev_ptr(mu, 0, n, "float64", "mu", d, True),
+                   _dev_ptr(mass_scale, 0, n, "float64", "mass_scale", d, True),
+                   _dev_ptr(ext_wrench, 6, n, "float64", "ext_wrench", d, True)]
 
     def forward(self, q, v, tau, mu=None, mass_scale=None, ext_wrench=None):
         """One force evaluation -> (vdot[18, N], force[12, N], contact[N] uint8 foot bits, flags[N]); q and v are not changed.
         Asynchronous on torch's current stream."""
-        import torch
         n, ins = self._inputs(q, v, tau, mu, mass_scale, ext_wrench)
-        dev = "cuda:%d" % self.device
-        vd = torch.empty((18, n), dtype=torch.float64, device=dev); f = torch.empty((12, n), dtype=torch.float64, device=dev)
-        ct = torch.empty((n,), dtype=torch.uint8, device=dev); fl = torch.empty((n,), dtype=torch.int32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(self._L.wbc_ground_forward(self._h, self._stream(), n, n, *ins, p(vd), p(f), p(ct), p(fl)))
-        return vd, f, ct, fl
+        outs, pouts = _outputs(None, _GROUND_OUTS, n, self.device)
+        _lib.check(self._L.wbc_ground_forward(self._h, self._stream(), n, n, *ins, *pouts))
+        return outs
 
     def step(self, q, v, tau, dt, time=None, mu=None, mass_scale=None, ext_wrench=None, counts=None, out=None):
         """One control period dt in substeps(dt) explicit substeps, in place on q, v (time += dt when given; counts[4, N] int32:
         row b += 1 when flag bit b is raised).  -> (force[12, N] mean over the substeps, contact[N] of the last substep, flags[N]);
         out: such a triple to write into."""
-        import torch
         n, ins = self._inputs(q, v, tau, mu, mass_scale, ext_wrench)
-        d = self.device
-        dev = "cuda:%d" % d
-        if out is None:
-            out = (torch.empty((12, n), dtype=torch.float64, device=dev), torch.empty((n,), dtype=torch.uint8, device=dev),
-                   torch.empty((n,), dtype=torch.int32, device=dev))
-        f, ct, fl = out
-        pt = _dev_ptr(time, 0, n, torch.float64, "time", d, True)
-        pc = _dev_ptr(counts, 4, n, torch.int32, "counts", d, True)
-        outs = [_dev_ptr(f, 12, n, torch.float64, "force", d), _dev_ptr(ct, 0, n, torch.uint8, "contact", d),
-                _dev_ptr(fl, 0, n, torch.int32, "flags", d)]
-        _lib.check(self._L.wbc_ground_step(self._h, self._stream(), n, n, float(dt), ins[0], ins[1], pt, *ins[2:], *outs, pc))
-        return f, ct, fl
+        pt = _dev_ptr(time, 0, n, "float64", "time", self.device, True)
+        pc = _dev_ptr(counts, 4, n, "int32", "counts", self.device, True)
+        outs, pouts = _outputs(out, _GROUND_STEP_OUTS, n, self.device)
+        _lib.check(self._L.wbc_ground_step(self._h, self._stream(), n, n, float(dt), ins[0], ins[1], pt, *ins[2:], *pouts, pc))
+        return outs
 
     def kernel_info(self):
         """Registers, scratch bytes per lane, LDS bytes and threads per block of the ground-step kernel."""
-        return self._kernel_info(self._L.wbc_ground_kernel_info)
+        return self._kernel_info("wbc_ground_kernel_info")
 
     def terrain_kernel_info(self):
         """kernel_info() of the step kernel that runs while a terrain is set."""
-        return self._kernel_info(self._L.wbc_ground_terrain_kernel_info)
+        return self._kernel_info("wbc_ground_terrain_kernel_info")
 
 
 @contextlib.contextmanager
@@ -297,7 +245,6 @@ def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=No
     mask are then the gait's at `time` (gait -> follow, if set -> tick -> plant step).  A GaitPlanner with a terrain
     (GaitPlanner.set_terrain) gives finished targets: with a follow mode set on a plant with a terrain this raises ValueError.
     Returns the last tick's (tau, metrics, status, targets, mask, force, flags), and for a GroundContactPlant also contact."""
-    import torch
     from .gait import GaitPlanner
     if ctrl.host_ptrs:
         raise ValueError("closed_loop: needs a device-pointer controller")
@@ -318,34 +265,38 @@ def closed_loop(ctrl, plant, traj, steps, dt, q, v, time, mu=None, mass_scale=No
             raise ValueError("closed_loop: the GaitPlanner lives on cuda:%d, the plant on cuda:%d" % (gait.device, d))
         if gait.has_terrain:
             gait._check_terrain_n(n)
-            if ground and getattr(plant, "_follow", "off") != "off" and plant._terrain is not None:
+            if plant._follow != "off" and plant._terrain is not None:
                 raise ValueError("closed_loop: the GaitPlanner has a terrain, so its targets are finished; the plant's follow mode %r "
                                  "would lift them a second time (set_follow('off'))" % (plant._follow,))
     htraj = None if gait is not None else traj._h
-    ptr = lambda a, rows, dt_, name, opt=False: _dev_ptr(a, rows, n, dt_, name, d, opt)
-    pq, pv, pt = ptr(q, 19, torch.float64, "q"), ptr(v, 18, torch.float64, "v"), ptr(time, 0, torch.float64, "time")
-    pmu, pms = ptr(mu, 0, torch.float64, "mu", True), ptr(mass_scale, 0, torch.float64, "mass_scale", True)
-    ppmu, ppms = ptr(plant_mu, 0, torch.float64, "plant_mu", True), ptr(plant_mass_scale, 0, torch.float64, "plant_mass_scale", True)
-    pc = ptr(counts, 4, torch.int32, "counts", True)
-    pw = ptr(ext_wrench, 6, torch.float64, "ext_wrench", True)
-    dev = q.device
-    tg = torch.empty((54, n), dtype=torch.float64, device=dev); mk = torch.empty((n,), dtype=torch.uint8, device=dev)
-    tau = torch.empty((12, n), dtype=torch.float64, device=dev); met = torch.empty((4, n), dtype=torch.float64, device=dev)
-    st = torch.empty((n,), dtype=torch.int32, device=dev)
-    f = torch.zeros((12, n), dtype=torch.float64, device=dev); fl = torch.zeros((n,), dtype=torch.int32, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    s = torch.cuda.current_stream(d).cuda_stream
+    ptr = lambda a, rows, dtype, name, opt=False: _dev_ptr(a, rows, n, dtype, name, d, opt)
+    pq, pv, pt = ptr(q, 19, "float64", "q"), ptr(v, 18, "float64", "v"), ptr(time, 0, "float64", "time")
+    pmu, pms = ptr(mu, 0, "float64", "mu", True), ptr(mass_scale, 0, "float64", "mass_scale", True)
+    ppmu, ppms = ptr(plant_mu, 0, "float64", "plant_mu", True), ptr(plant_mass_scale, 0, "float64", "plant_mass_scale", True)
+    pc = ptr(counts, 4, "int32", "counts", True)
+
+    def fresh(specs, zero=False):
+        """Fresh outputs beside q -> (tensors, their pointers, taken as the caller's tensors' are)"""
+        ts = [_lib.new_out(rows, n, dtype, q.device, zero) for rows, dtype, _ in specs]
+        return ts, [ptr(t, rows, dtype, name) for t, (rows, dtype, name) in zip(ts, specs)]
+
+    (tg, mk), (ptg, pmk) = fresh(_lib.TARGET_OUTS)
+    (tau, met, st), ptick = fresh(_lib.TICK_OUTS)
+    # what only the ground has sits in lists of one or none: the wrench among the arguments, the contact between force and flags.
+    # The plant's outputs are zeroed: with steps == 0 the caller sees them unwritten.
     if ground:
-        ct = torch.zeros((n,), dtype=torch.uint8, device=dev)
-        with _gait_set(plant, "wbc_ground_set_gait", gait):
-            _lib.check(plant._L.wbc_ground_rollout(ctrl._h, plant._h, htraj, C.c_void_p(s), int(steps), float(dt), n, n, pq, pv, pt, p(tg),
-                                                   p(mk), pmu, pms, ppmu, ppms, pw, p(tau), p(met), p(st), p(f), p(ct), p(fl), pc))
-        ctrl._bound_stream = s
-        ctrl._keep = (tg, mk, tau, met, st, f, fl, ct, mu, mass_scale, plant_mu, plant_mass_scale, ext_wrench)
-        return tau, met, st, tg, mk, f, fl, ct
-    with _gait_set(plant, "wbc_plant_set_gait", gait):
-        _lib.check(plant._L.wbc_plant_rollout(ctrl._h, plant._h, htraj, C.c_void_p(s), int(steps), float(dt), n, n, pq, pv, pt, p(tg),
-                                              p(mk), pmu, pms, ppmu, ppms, p(tau), p(met), p(st), p(f), p(fl), pc))
-    ctrl._bound_stream = s   # wbc_plant_rollout bound the controller to this stream (wbc_set_stream)
-    ctrl._keep = (tg, mk, tau, met, st, f, fl, mu, mass_scale, plant_mu, plant_mass_scale)
-    return tau, met, st, tg, mk, f, fl
+        (f, ct, fl), pplant = fresh(_GROUND_STEP_OUTS, zero=True)
+        rollout, set_gait, contact = "wbc_ground_rollout", "wbc_ground_set_gait", [ct]
+        wrench, pwrench = [ext_wrench], [ptr(ext_wrench, 6, "float64", "ext_wrench", True)]
+    else:
+        (f, fl), pplant = fresh(_RIGID_LOOP_OUTS, zero=True)
+        rollout, set_gait, contact = "wbc_plant_rollout", "wbc_plant_set_gait", []
+        wrench, pwrench = [], []
+    s = _lib.stream_of(d)
+    with _gait_set(plant, set_gait, gait):
+        _lib.check(getattr(plant._L, rollout)(ctrl._h, plant._h, htraj, C.c_void_p(s), int(steps), float(dt), n, n, pq, pv, pt, ptg, pmk,
+                                              pmu, pms, ppmu, ppms, *pwrench, *ptick, *pplant, pc))
+    # The rollout bound the controller to this stream (wbc_set_stream).  Through the class: whatever stands in for a controller here
+    # need hold no more than host_ptrs and _h.
+    BatchedController._adopt(ctrl, s, (tg, mk, tau, met, st, f, fl, *contact, mu, mass_scale, plant_mu, plant_mass_scale, *wrench))
+    return (tau, met, st, tg, mk, f, fl, *contact)

@@ -7,10 +7,12 @@ steep segment.  The constructors mirror the terrains the reference ships for its
 towr/include/towr/terrain/examples/height_map_examples.h); the numbers are this project's own.  `GroundContactPlant.set_terrain`
 takes a list of up to 16 profiles; each instance picks one by `terrain_id` and scales it by `terrain_scale`.
 """
+import ctypes as C
 import math
 
 import numpy as np
 
+from . import _lib
 from ._lib import WbcTerrainProfile   # wbc_terrain_profile of include/wbc_ground.h
 
 MAX_KNOTS = 8
@@ -55,6 +57,31 @@ def c_array(profiles):
     for i, p in enumerate(profiles):
         arr[i] = p.c_struct()
     return arr
+
+
+def bind(profiles, terrain_id, terrain_scale, device, owner, hint=""):
+    """What GroundContactPlant.set_terrain and GaitPlanner.set_terrain share: 1 .. 16 profiles, terrain_id (uint8 [N]) and terrain_scale
+    (float64 [N]) on cuda:`device`, where `owner` lives, N read off whichever of the two is given.
+    -> (wbc_terrain_profile array as void*, count, terrain_id's pointer, terrain_scale's, the tuple (profiles, terrain_id, terrain_scale, N)
+    that the setter stores: it keeps the tensors alive and _check_terrain_n reads its N)"""
+    import torch
+    profiles = list(profiles) if profiles is not None else []
+    if not profiles or not all(isinstance(p, Profile) for p in profiles):
+        raise ValueError("set_terrain: profiles must be a non-empty list of terrain.Profile" + hint)
+    n = None
+    for a in (terrain_id, terrain_scale):
+        if a is not None and isinstance(a, torch.Tensor) and a.dim() == 1:
+            n = int(a.shape[0]) if n is None else n
+    pid = _lib.dev_ptr(terrain_id, 0, n, "uint8", "terrain_id", device, owner, True)
+    psc = _lib.dev_ptr(terrain_scale, 0, n, "float64", "terrain_scale", device, owner, True)
+    return C.cast(c_array(profiles), C.c_void_p), len(profiles), pid, psc, (profiles, terrain_id, terrain_scale, n)
+
+
+def _check_terrain_n(terrain, n, refuses, whose=""):
+    """terrain: what a set_terrain stored, or None; refuses(held, n): the owner's rule, operator.lt for the plant, which takes a prefix of
+    a longer terrain, operator.ne for the planner"""
+    if terrain is not None and terrain[3] is not None and refuses(terrain[3], n):
+        raise ValueError("%sterrain_id / terrain_scale hold %d instances, the call has %d" % (whose, terrain[3], n))
 
 
 def flat(height=0.0, **kw):

@@ -31,8 +31,10 @@ def decode_trunk_state(buf):
                 contact=[bool(c) for c in s.contact], foot_f=a2(s.foot_f), targets=t, contact_mask=int(m.value))
 
 
-class TrunkTrajectory:
+class TrunkTrajectory(_lib.Handle):
     """Device-resident trajectory table + nearest-timestamp lookup (planners/towr.py:92-106)."""
+
+    _destroy = "wbc_traj_destroy"
 
     def __init__(self, timestamps, targets, masks, model="mini_cheetah", wait_time=1.0, device=0,
                  standing_targets=None, standing_mask=0b1111):
@@ -59,31 +61,10 @@ class TrunkTrajectory:
     def lookup(self, time, out=None):
         """time: CUDA float64 tensor [n] -> (targets [54, n], contact_mask [n]) on the current stream."""
         import torch
-        if not (isinstance(time, torch.Tensor) and time.is_cuda and time.dtype == torch.float64 and time.is_contiguous()
-                and time.dim() == 1 and time.device.index == self.device):
-            raise ValueError("time: expected a contiguous float64 CUDA tensor [n] on device %d" % self.device)
+        if not (isinstance(time, torch.Tensor) and time.dim() == 1):
+            raise ValueError("time: expected a CUDA tensor of shape [n]")
         n = int(time.shape[0])
-        if out is not None:
-            tg, mk = out
-            ok = (tg.is_cuda and tg.dtype == torch.float64 and tg.is_contiguous() and tuple(tg.shape) == (54, n) and
-                  mk.is_cuda and mk.dtype == torch.uint8 and mk.is_contiguous() and tuple(mk.shape) == (n,))
-            if not ok:
-                raise ValueError("out: expected (float64 [54, n], uint8 [n]) contiguous CUDA tensors")
-        if out is None:
-            dev = time.device
-            out = (torch.empty((54, n), dtype=torch.float64, device=dev), torch.empty((n,), dtype=torch.uint8, device=dev))
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._L.wbc_traj_lookup(self._h, C.c_void_p(stream), n, n, C.c_void_p(time.data_ptr()),
-                                           C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr())))
+        pt = _lib.dev_ptr(time, 0, n, "float64", "time", self.device, "the trajectory")
+        out, pouts = _lib.outputs(out, _lib.TARGET_OUTS, n, self.device, "the trajectory")
+        _lib.check(self._L.wbc_traj_lookup(self._h, self._stream(), n, n, pt, *pouts))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.wbc_traj_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
