@@ -44,6 +44,11 @@ extern int* g_gi_adds;      // tests: [32] per robot = how many rows the active 
 #endif
 // block placement: a condition that is almost never true (the exits of the active set's fast chain) -- its code is laid out after the hot path, which falls through
 #define WBC_UNLIKELY(x) __builtin_expect(!!(x), 0)
+// The same for the tick's own wave-uniform forks, where `on` is a compile-time flag of the instantiation (hex_tick: STRAIGHT): the expectation is
+// stated only in the kernels whose emitted code it leaves within the registers they had without it.  (A macro, not a function: the expectation
+// is consumed before inlining and would be lost inside a callee.)
+#define WBC_LIKELY_IF(on, x) ((on) ? __builtin_expect(!!(x), 1) : !!(x))
+#define WBC_UNLIKELY_IF(on, x) ((on) ? __builtin_expect(!!(x), 0) : !!(x))
 #ifndef WBC_GI_FORCE_BAIL
 #ifdef WBC_DEV_FORCE_BAIL   // diagnostic device builds: every wavefront leaves the fast path at trip WBC_DEV_FORCE_BAIL
 #define WBC_GI_FORCE_BAIL(qc) ((qc) == WBC_DEV_FORCE_BAIL)
@@ -870,6 +875,12 @@ WBC_HD int hex_tick(const ModelC& m, const ParamsX& P, Q& qo, In in, unsigned ma
   const int l = h >> 2, sb = h & 3;
   const bool ct = (mask >> l) & 1u;
   constexpr bool MP = (KIND == KIND_MPTC || KIND == KIND_PC);   // task-space passivity laws (xi passes, Lambda)
+  // Block placement of the forks every wavefront of the task-space laws' headline batches passes the same way (the 24-row append, no status-2 exit, no
+  // copy of y): in the launch-per-tick MPTC and PC kernels without a torque box the side a trot runs falls through and the other one is laid out behind.
+  // Not in the ID and CLF ticks: they have no 24 / 30-row fork, and the batch ID is measured on is a stand, whose deep robots DO copy y -- stated there
+  // the expectation was wrong and the ID stand read +0.5 % (profiles/r22/README.md).  The torque-box ticks and the rollout kernels keep the compiler's
+  // own placement too: stated there, the same expectations cost registers (up to +9 AGPRs, and 8 bytes of scratch in one rollout kernel).
+  constexpr bool STRAIGHT = MP && !TB && !WARM;
   constexpr int NV = (KIND == KIND_CLF) ? NZ + 1 : NZ;          // reduced variables: z (12) [+ slack delta]
   const bool colv = sb < 3;  // owns a z-space column (else: the right-hand-side / ab0 column, or delta)
   const bool cold = (KIND == KIND_CLF) && h == HEX_DELTA_LANE;   // owns the delta column (CLF law)
@@ -1467,7 +1478,8 @@ WBC_HD int hex_tick(const ModelC& m, const ParamsX& P, Q& qo, In in, unsigned ma
   // (A third instantiation over 18 rows for wavefronts where nobody swings was measured: nothing on the MPTC stand, whose launch is
   // the active set's, and +4 % on the trot through the larger code -- not kept.)
   const unsigned ncontact = (mask & 1u) + ((mask >> 1) & 1u) + ((mask >> 2) & 1u) + ((mask >> 3) & 1u);
-  if (P1 == 18 && !qo.wave_any(ncontact < 2u)) {
+  // (placement: the 24-row body falls through; the 30-row one -- a wavefront holding a robot with three swing legs -- is laid out behind the tick)
+  if (P1 == 18 && WBC_LIKELY_IF(STRAIGHT, !qo.wave_any(ncontact < 2u))) {
     const bool s0 = !(mask & 1u), s1 = !(mask & 2u), s2 = !(mask & 4u);
     double A24[24];
     for (int i = 0; i < 6; i++) A24[i] = Acol[i];
@@ -1500,7 +1512,7 @@ WBC_HD int hex_tick(const ModelC& m, const ParamsX& P, Q& qo, In in, unsigned ma
     const double rmax = qo.max16((colv || cold) ? ainv : 0.0), rmin = qo.min16((colv || cold) ? ainv : HEX_NONE);
     // rmin/rmax here are of 1/|R_cc|:  min|R| / max|R| = rmin / rmax;  a zero pivot gives inf/nan -> singular
     if (!(rmin > 1e-13 * rmax) || !(rmax < 1e300)) status = ST_SINGULAR;
-    if (status == ST_SINGULAR) {
+    if (WBC_UNLIKELY_IF(STRAIGHT, status == ST_SINGULAR)) {
       // reported, not solved: zero torques AND zero accelerations (include/wbc.h: every step writes vd; a rollout
       // integrates them, so they must be defined); a malformed instance has no position error to report either
       if (colv) out_tau(m.act_inv[3 * l + sb], 0.0);
@@ -1535,7 +1547,7 @@ WBC_HD int hex_tick(const ModelC& m, const ParamsX& P, Q& qo, In in, unsigned ma
     // lane (0, 3) owns no row of J: its row slots carry y = Q'b (the right-hand-side column after the append) through the active
     // set's reflections, for the evaluation of z after a drop (hex_gi)
     // (only a robot with three or four feet down is ever evaluated that way -- `deep` in hex_gi -- so a wavefront of trotting robots skips the copy)
-    if (qo.wave_any(((mask & 1u) + ((mask >> 1) & 1u) + ((mask >> 2) & 1u) + ((mask >> 3) & 1u)) >= 3u)) {
+    if (WBC_UNLIKELY_IF(STRAIGHT, qo.wave_any(((mask & 1u) + ((mask >> 1) & 1u) + ((mask >> 2) & 1u) + ((mask >> 3) & 1u)) >= 3u))) {
 #pragma unroll
       for (int c = 0; c < NV; c++) Jr[c] = (h == 3) ? Rcol[c] : Jr[c];
     }
